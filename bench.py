@@ -13,15 +13,24 @@ sharded over the ranks (total work fixed -> "strong" scaling).
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8 ...
     python bench.py --workload c5            # BASELINE config 5 on its own (128 lockstep fits of 4096 x 512)
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra
-objects: "roofline" for the dominant kernel (the fp64-MFMA SYRK J^T J, timed
-with HIP events on the stream it runs on) and "cpu_baseline" (the numpy oracle
-timed on this box's host cores on a bounded sample; a baseline, not a target).
-On one GPU the headline run (workload c4) also measures the other BASELINE.json
-configurations -- c2, c3, c5 and the shape every rank of an 8-GPU run sees
-(shard8192) -- each with its step time, its dominant kernel's roofline and a
-chi2 match against the CPU port: config.other_workloads (SURVEY.md 8d "reported
-per config"; --no-others skips them).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times exactly
+--steps steps and prints the line: value,
+ms_per_step and "roofline" for the dominant kernel (the fp64-MFMA SYRK J^T J,
+timed with HIP events on the stream it runs on, inside the timed region; shapes
+with P <= 1024 replay captured graphs there and have no phase times).
+--dump-outputs DIR also writes what the last timed step computed (the point,
+the residuals, J^T f and a fixed sample of rows of J^T J) to DIR/<name>.npy;
+the inputs are seeded, so two builds can be compared array for array.
+
+--full adds everything else, outside the timed region: "cpu_baseline" (the
+numpy oracle timed on the host's cores on a bounded sample; a baseline, not a
+target) with config.chi2_match, config.whole_fit, the second, instrumented
+pass that gives small shapes their phase times, and -- on one GPU, workload c4
+-- the other BASELINE.json configurations c2, c3, c5 and the shape every rank
+of an 8-GPU run sees (shard8192), each with its step time, its dominant
+kernel's roofline and a chi2 match against the CPU port:
+config.other_workloads (SURVEY.md 8d "reported per config"; --no-others,
+--no-cpu-baseline and --whole-fit-maxit 0 skip parts of it).
 """
 import argparse
 import json
@@ -60,6 +69,11 @@ def parse():
     ap.add_argument('--workload', default='c4', choices=sorted(WORKLOADS))
     ap.add_argument('--ndata', type=int, default=0, help='override N_data (debug)')
     ap.add_argument('--nparam', type=int, default=0, help='override N_param (debug)')
+    ap.add_argument('--full', action='store_true',
+                    help='beside the headline: the CPU baseline and chi2 matches, the other workloads, the whole fits, and the '
+                         'roofline figures that take a pass of their own (a plain run times the steps and prints the line)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last of them computed to DIR/<name>.npy (float64)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-others', action='store_true', help='headline only: skip config.other_workloads (c2, c3, c5, shard8192)')
     ap.add_argument('--two-pass', action='store_true', help='time the steps without phase timers, the phases in a second pass (always so for P <= 1024 on one rank)')
@@ -67,7 +81,10 @@ def parse():
     ap.add_argument('--whole-fit-maxit', type=int, default=200, help='iteration cap of the whole fits reported in config.whole_fit (0: skip them)')
     ap.add_argument('--whole-fit-algs', default='dogleg,ddogleg,subspace2D,lmaccel',
                     help='other trust-region methods the whole fit is repeated with (config.whole_fit.by_algorithm; empty: none)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:      # a plain run: the headline only (no CPU legs, no companions; lm_workload / c5_workload skip their extra passes)
+        args.no_cpu_baseline = args.no_others = True
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -234,6 +251,25 @@ def workload_label(name, N, P, block, dense_prior, world):
         'dense correlated' if dense_prior else 'diagonal', world, '' if world == 1 else 's')
 
 
+DUMP_JTJ_ROWS = 512     # rows of J^T J that --dump-outputs keeps (all of them when P is smaller)
+
+
+def last_step_outputs(pr):
+    """What a caller of lsqamd_step holds after the last timed step, through the getters of include/lsqfit_amd.h: the point
+    (lsqamd_get_x), the whitened data residuals there (lsqamd_get_f; this rank's rows), J^T f (lsqamd_get_grad) and J^T J
+    (lsqamd_get_jtj) -- of the last, a fixed seeded sample of rows (4096 x 4096 doubles are 134 MB), named in jtj_rows."""
+    P = pr.P
+    rows = np.sort(np.random.Generator(np.random.PCG64(20260)).choice(P, size=min(P, DUMP_JTJ_ROWS), replace=False))
+    return {'x': pr.get_x(), 'f': pr.get_f_data(), 'grad': pr.get_grad(), 'jtj_sample': pr.get_jtj()[rows],
+            'jtj_rows': rows.astype(np.float64)}
+
+
+def dump_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def lm_workload(name, args, env, steps, warmup, headline):
     """K accepted LM steps of one single-fit workload on this rank's rows.  -> (line, ctx): `line` is the bench line's body
     (headline) or the compact entry of config.other_workloads; ctx keeps the problem for the CPU-baseline / chi2 leg."""
@@ -348,18 +384,20 @@ def lm_workload(name, args, env, steps, warmup, headline):
         barrier()
         regions.append((time.perf_counter() - t0, state['reinits']))
     elapsed, reinits_timed = sorted(regions)[len(regions) // 2]
-    if two_pass:
+    if headline and args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step_outputs(pr))
+    if two_pass and args.full:
         pr.timing(True)
         pr.timing_reset()
         for _ in range(steps):
             one_step()
         torch.cuda.synchronize()
     state['reinits'] = reinits_timed
-    tm = pr.timings()
+    tm = pr.timings()           # (a plain run of a two-pass shape has no phase times: every count is 0)
     pr.timing(False)
     s = _lib.Summary()
     lib.lsqamd_finish(h, C.byref(s))
-    whole_fit = whole_fits(args, env, pr, d, wh, P) if headline and args.whole_fit_maxit > 0 else None
+    whole_fit = whole_fits(args, env, pr, d, wh, P) if headline and args.full and args.whole_fit_maxit > 0 else None
     pr.set_options((1e-8, 1e-10, 1e-10), 1000)
     reduce_ms = [tm['reduce'][0] / max(1, tm['reduce'][1])]
     step_ms = [1e3 * elapsed / steps]
@@ -433,8 +471,10 @@ def lm_workload(name, args, env, steps, warmup, headline):
                'frac': step_flops / (elapsed / steps) / 1e12 / PEAK_FP64_MFMA_TFLOPS,
                'note': 'algorithmic flops of one accepted step on this rank (SYRK + whitening + Cholesky + '
                        'J^T f + solve; rejected trials and model evaluation not counted) over the wall-clock step'}
-    timing_pass = ('a second, instrumented pass of %d steps right after the timed region (the timed region '
-                   'itself replays captured graphs without event records)' % steps) if two_pass else 'HIP events inside the timed region'
+    timing_pass = 'HIP events inside the timed region'
+    if two_pass:
+        timing_pass = ('a second, instrumented pass of %d steps right after the timed region (the timed region '
+                       'itself replays captured graphs without event records)' % steps) if args.full else 'none (--full times the phases in a second pass)'
     phases = {k: (v[0] / v[1] if v[1] else None) for k, v in tm.items()}
     calls = {k: v[1] for k, v in tm.items()}
     exch = {'exposed_share_per_rank': exposed, 'collective_ms_per_exchange_per_rank': coll_per_step,
@@ -598,11 +638,11 @@ def whole_fits(args, env, pr, d, wh, P):
     return whole_fit
 
 
-def c5_workload(args, env, runs=3):
+def c5_workload(args, env, runs=3, headline=False):
     """BASELINE config 5: 128 fits of (4096, 512) that differ in the prior width of the amplitudes, in lockstep on one GPU
     (lsqamdb_*: one captured hipGraph per round of the batch).  A "step" here is one lockstep round = one trial LM step of every
-    still-active fit.  Timed: `runs` whole sweeps (wall clock around lsqamdb_run, inputs resident); then one instrumented sweep
-    (eager rounds, HIP events around the batched J^T J launch) for the roofline of the dominant kernel."""
+    still-active fit.  Timed: `runs` whole sweeps (wall clock around lsqamdb_run, inputs resident); then, with --full, one instrumented
+    sweep (eager rounds, HIP events around the batched J^T J launch) for the roofline of the dominant kernel."""
     import lsqfit_amd as amd
     from lsqfit_amd import synth
     torch = env['torch']
@@ -630,6 +670,20 @@ def c5_workload(args, env, runs=3):
         dev_ms.append(out['device_ms'])
     total_rounds, total_s = int(sum(rounds)), float(sum(walls))
     fit_steps = int(out['nit'].sum())
+    if headline and args.dump_outputs:      # what the last timed sweep returned
+        dump_outputs(args.dump_outputs, {k: out[k] for k in ('pmean', 'chi2', 'nit', 'nfev', 'stopping_criterion')})
+    line = {'workload': 'c5: %d lockstep fits of cosmix N_data=%d N_param=%d, diagonal data covariance, per-fit prior widths, '
+                        'hipGraph-captured rounds, 1 GPU' % (B, N, P),
+            'ms_per_step': 1e3 * total_s / total_rounds, 'value': total_rounds / total_s, 'unit': 'lockstep LM rounds/s (x %d fits)' % B,
+            'steps': total_rounds, 'sweeps_timed': runs, 'ms_per_sweep': 1e3 * total_s / runs, 'device_ms_per_sweep': float(np.mean(dev_ms)),
+            'rounds_per_sweep': int(rounds[-1]), 'graph_rounds_per_sweep': int(out['graph_rounds']),
+            'fit_steps_per_sweep': fit_steps, 'fit_steps_per_s': fit_steps * runs / total_s,
+            'nit_min_max': [int(out['nit'].min()), int(out['nit'].max())], 'all_converged': bool(np.all(out['stopping_criterion'] >= 1)),
+            'setup_s': round(t_setup, 3), 'generate_s': round(t_generate, 3), 'roofline': None}
+    line['_chi2_inputs'] = (d, pm, ps, out['chi2'].copy(), out['nit'].copy())
+    if not args.full:      # the roofline below takes a sweep of its own
+        bf.close()
+        return line
     bf.timing(True)
     ti = bf.run(covariance=False)
     tms = bf.timings()
@@ -639,23 +693,14 @@ def c5_workload(args, env, runs=3):
     flops_total = float(ti['njev'].sum()) * N * P * (P + 1)
     ach = flops_total / (syrk_ms * 1e-3) / 1e12 if syrk_ms > 0 else 0.0
     chol_ms, chol_n = tms['cholesky']
-    line = {'workload': 'c5: %d lockstep fits of cosmix N_data=%d N_param=%d, diagonal data covariance, per-fit prior widths, '
-                        'hipGraph-captured rounds, 1 GPU' % (B, N, P),
-            'ms_per_step': 1e3 * total_s / total_rounds, 'value': total_rounds / total_s, 'unit': 'lockstep LM rounds/s (x %d fits)' % B,
-            'steps': total_rounds, 'sweeps_timed': runs, 'ms_per_sweep': 1e3 * total_s / runs, 'device_ms_per_sweep': float(np.mean(dev_ms)),
-            'rounds_per_sweep': int(rounds[-1]), 'graph_rounds_per_sweep': int(out['graph_rounds']),
-            'fit_steps_per_sweep': fit_steps, 'fit_steps_per_s': fit_steps * runs / total_s,
-            'nit_min_max': [int(out['nit'].min()), int(out['nit'].max())], 'all_converged': bool(np.all(out['stopping_criterion'] >= 1)),
-            'setup_s': round(t_setup, 3), 'generate_s': round(t_generate, 3),
-            'roofline': {'phase': 'batched J^T J', 'kernel': 'gemm_tn_f64_interior_kernel<false, true, true> (batched over the fits that moved)',
-                         'bound': 'mfma', 'flops_per_launch': flops_total / max(1, syrk_n), 'launches': int(syrk_n),
-                         'avg_launch_ms': syrk_ms / max(1, syrk_n), 'achieved': ach, 'peak': PEAK_FP64_MFMA_TFLOPS, 'unit': 'TFLOP/s',
-                         'frac': ach / PEAK_FP64_MFMA_TFLOPS,
-                         'timing_pass': 'one extra sweep with eager rounds and HIP events around every batched J^T J launch (the timed sweeps replay graphs)',
-                         'per_kernel': {'potrf_upper_batched': {'bound': 'mfma', 'ms': chol_ms / max(1, chol_n), 'launches': int(chol_n),
-                                                                 'flops': float(ti['nfev'].sum() - B) * P ** 3 / 3.0 / max(1, chol_n),
-                                                                 'frac': (float(ti['nfev'].sum() - B) * P ** 3 / 3.0) / max(chol_ms * 1e-3, 1e-30) / 1e12 / PEAK_FP64_MFMA_TFLOPS}}}}
-    line['_chi2_inputs'] = (d, pm, ps, out['chi2'].copy(), out['nit'].copy())
+    line['roofline'] = {'phase': 'batched J^T J', 'kernel': 'gemm_tn_f64_interior_kernel<false, true, true> (batched over the fits that moved)',
+                    'bound': 'mfma', 'flops_per_launch': flops_total / max(1, syrk_n), 'launches': int(syrk_n),
+                    'avg_launch_ms': syrk_ms / max(1, syrk_n), 'achieved': ach, 'peak': PEAK_FP64_MFMA_TFLOPS, 'unit': 'TFLOP/s',
+                    'frac': ach / PEAK_FP64_MFMA_TFLOPS,
+                    'timing_pass': 'one extra sweep with eager rounds and HIP events around every batched J^T J launch (the timed sweeps replay graphs)',
+                    'per_kernel': {'potrf_upper_batched': {'bound': 'mfma', 'ms': chol_ms / max(1, chol_n), 'launches': int(chol_n),
+                                                            'flops': float(ti['nfev'].sum() - B) * P ** 3 / 3.0 / max(1, chol_n),
+                                                            'frac': (float(ti['nfev'].sum() - B) * P ** 3 / 3.0) / max(chol_ms * 1e-3, 1e-30) / 1e12 / PEAK_FP64_MFMA_TFLOPS}}}
     bf.close()
     return line
 
@@ -726,7 +771,7 @@ def main():
         # exchange; the line is measured on one GPU
         if world > 1:
             raise SystemExit('bench.py: --workload c5 is a one-GPU measurement (independent fits: N GPUs run N shares, no collective)')
-        c5 = c5_workload(args, env, runs=max(1, args.steps // 20))
+        c5 = c5_workload(args, env, runs=max(1, args.steps // 20), headline=True)
         if args.no_cpu_baseline:
             c5.pop('_chi2_inputs')
         else:

@@ -21,7 +21,7 @@ def last_json(out):
 
 
 def test_single_process_line():
-    r = subprocess.run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '1', '--ndata', '4096', '--nparam',
+    r = subprocess.run([sys.executable, 'bench.py', '--full', '--steps', '3', '--warmup', '1', '--ndata', '4096', '--nparam',
                         '256', '--cpu-seconds', '1'], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = last_json(r.stdout)
@@ -40,6 +40,35 @@ def test_single_process_line():
     assert 'other_workloads' not in d['config']            # (debug shapes: the headline's companions are not measured)
     fq = cb['faithful_qr_1thread']
     assert fq['cores'] == 1 and fq['extrapolated'] and 0 < fq['value'] < cb['value'] * 100
+
+
+def test_plain_run_is_the_headline_only_and_dumps_what_the_last_step_computed(tmp_path):
+    """Without --full: set-up, warm-up, exactly --steps timed steps, the line -- no CPU baseline, no chi2 match, no whole fit, no
+    companions.  --dump-outputs writes the last step's point, residuals, J^T f and sampled rows of J^T J as float64 .npy files;
+    the inputs are seeded, so two runs with the same arguments (started side by side here) write identical arrays."""
+    import numpy as np
+    N, P = 4096, 256
+    runs = [subprocess.Popen([sys.executable, 'bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1', '--ndata', str(N), '--nparam', str(P),
+                              '--dump-outputs', str(tmp_path / name)], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+            for name in ('a', 'b')]
+    outs = [r.communicate(timeout=600) for r in runs]
+    for r, (so, se) in zip(runs, outs):
+        assert r.returncode == 0, se[-2000:]
+        d = last_json(so)
+        assert KEYS <= set(d) and d['steps'] == 3 and d['warmup'] == 1 and d['dtype'] == 'f64' and d['higher_is_better'] is True
+        assert d['value'] > 0 and abs(d['value'] * d['ms_per_step'] / 1e3 - 1) < 1e-9
+        assert d['cpu_baseline'] is None and d['config']['whole_fit'] is None
+        assert 'chi2_match' not in d['config'] and 'other_workloads' not in d['config']
+    a, b = ({n[:-4]: np.load(str(tmp_path / name / n)) for n in sorted(os.listdir(str(tmp_path / name)))} for name in ('a', 'b'))
+    assert set(a) == set(b) == {'x', 'f', 'grad', 'jtj_sample', 'jtj_rows'}
+    assert a['x'].shape == (P,) and a['f'].shape == (N,) and a['grad'].shape == (P,) and a['jtj_sample'].shape == (P, P)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype == np.float64 and np.isfinite(a[k]).all() and np.array_equal(a[k], b[k]), k
+    rows = a['jtj_rows'].astype(int)
+    assert np.array_equal(rows, np.arange(P))                 # (P <= 512: every row is kept)
+    J = a['jtj_sample']
+    assert np.array_equal(J, J.T) and np.all(np.diag(J) > 0) and np.any(a['x'] != 0) and np.any(a['f'] != 0)
 
 
 def test_two_rank_launch_line():
@@ -88,9 +117,9 @@ def test_two_rank_self_launch_through_the_library_collective(tmp_path):
 
 
 def test_config5_line():
-    """`python bench.py --workload c5`: BASELINE config 5 (128 lockstep fits of 4096 x 512) as a bench line of its own -- step = one
+    """`python bench.py --full --workload c5`: BASELINE config 5 (128 lockstep fits of 4096 x 512) as a bench line of its own -- step = one
     lockstep round, the batched J^T J launch's roofline from HIP events, chi2 of the first and last fit against the CPU port."""
-    r = subprocess.run([sys.executable, 'bench.py', '--workload', 'c5'], cwd=ROOT, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, 'bench.py', '--full', '--workload', 'c5'], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = last_json(r.stdout)
     assert KEYS <= set(d) and d['n_gpus'] == 1 and d['dtype'] == 'f64' and '(4096,512)' in d['metric']

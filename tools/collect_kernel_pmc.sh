@@ -21,10 +21,10 @@ TAGS=${LSQAMD_PMC_TAGS:-"potrf whiten c5"}      # (+ c3: the triangular whitenin
 for tag in $TAGS; do
   case $tag in
     potrf)  prog=(python3 $ROOT/tools/time_potrf.py) ;;
-    whiten) prog=(python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline) ;;
+    whiten) prog=(python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline) ;;
     c5)     prog=(python3 $ROOT/tools/run_c5.py nograph) ;;
-    c3)     prog=(python3 $ROOT/bench.py --workload c3 --steps 10 --warmup 2 --no-cpu-baseline --two-pass) ;;
-    shard)  prog=(python3 $ROOT/bench.py --ndata 8192 --steps 6 --warmup 2 --no-cpu-baseline --whole-fit-maxit 0) ;;
+    c3)     prog=(python3 $ROOT/bench.py --full --workload c3 --steps 10 --warmup 2 --no-cpu-baseline --two-pass) ;;
+    shard)  prog=(python3 $ROOT/bench.py --full --ndata 8192 --steps 6 --warmup 2 --no-cpu-baseline --whole-fit-maxit 0) ;;
   esac
   run $tag sq "$SQ" "${prog[@]}"
   run $tag sq2 "$SQ2" "${prog[@]}"

@@ -7,20 +7,20 @@ R=${LSQAMD_ROUND:-r06}
 OUT=$ROOT/gpurun_out/prof_$R
 mkdir -p $OUT
 cd $ROOT
-python3 bench.py --steps 20 --warmup 5 > $OUT/${R}_bench_default.json 2> $OUT/bench_c4.err      # the driver's command: c4 headline + config.other_workloads
-python3 bench.py --workload shard8192 --steps 40 --warmup 5 --no-cpu-baseline | grep '^{' > $OUT/${R}_bench_shard8192_1gpu.json 2>/dev/null
-python3 bench.py --workload c5 | grep '^{' > $OUT/${R}_bench_c5_1gpu.json 2>/dev/null
-python3 bench.py --workload c2 --steps 200 --warmup 20 --cpu-seconds 5 > $OUT/${R}_bench_c2_1gpu.json 2>/dev/null
-python3 bench.py --workload c3 --steps 40 --warmup 5 --cpu-seconds 10 > $OUT/${R}_bench_c3_1gpu.json 2>/dev/null
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/${R}_bench_default.json 2> $OUT/bench_c4.err      # c4 headline + config.other_workloads, CPU baseline, whole fits
+python3 bench.py --full --workload shard8192 --steps 40 --warmup 5 --no-cpu-baseline | grep '^{' > $OUT/${R}_bench_shard8192_1gpu.json 2>/dev/null
+python3 bench.py --full --workload c5 | grep '^{' > $OUT/${R}_bench_c5_1gpu.json 2>/dev/null
+python3 bench.py --full --workload c2 --steps 200 --warmup 20 --cpu-seconds 5 > $OUT/${R}_bench_c2_1gpu.json 2>/dev/null
+python3 bench.py --full --workload c3 --steps 40 --warmup 5 --cpu-seconds 10 > $OUT/${R}_bench_c3_1gpu.json 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c4 -- python3 $ROOT/bench.py --steps 8 --warmup 2 --no-cpu-baseline > $OUT/${R}_bench_c4_1gpu_under_rocprof.json 2> $OUT/trace_c4.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c4 -- python3 $ROOT/bench.py --full --steps 8 --warmup 2 --no-cpu-baseline > $OUT/${R}_bench_c4_1gpu_under_rocprof.json 2> $OUT/trace_c4.err
 cp $(find $OUT/trace_c4 -name "*kernel_stats.csv" | head -1) $OUT/${R}_c4_1gpu_kernel_stats.csv
 PYTHONPATH=$ROOT rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_tape -- python3 $ROOT/tools/time_tape.py > $OUT/tape_default.txt 2> $OUT/trace_tape.err
 cp $(find $OUT/trace_tape -name "*kernel_stats.csv" | head -1) $OUT/${R}_tape_n65536_kernel_stats.csv
 # kernel stats of the other BASELINE configs: c2 (4096, 256), c3 (8192, 1024, one dense block), c5 (128 batched fits of 4096 x 512)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c2 -- python3 $ROOT/bench.py --workload c2 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/${R}_bench_c2_1gpu_under_rocprof.json 2> $OUT/trace_c2.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c2 -- python3 $ROOT/bench.py --full --workload c2 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/${R}_bench_c2_1gpu_under_rocprof.json 2> $OUT/trace_c2.err
 cp $(find $OUT/trace_c2 -name "*kernel_stats.csv" | head -1) $OUT/${R}_c2_1gpu_kernel_stats.csv
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c3 -- python3 $ROOT/bench.py --workload c3 --steps 40 --warmup 5 --no-cpu-baseline > $OUT/${R}_bench_c3_1gpu_under_rocprof.json 2> $OUT/trace_c3.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c3 -- python3 $ROOT/bench.py --full --workload c3 --steps 40 --warmup 5 --no-cpu-baseline > $OUT/${R}_bench_c3_1gpu_under_rocprof.json 2> $OUT/trace_c3.err
 cp $(find $OUT/trace_c3 -name "*kernel_stats.csv" | head -1) $OUT/${R}_c3_1gpu_kernel_stats.csv
 PYTHONPATH=$ROOT rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c5 -- python3 $ROOT/tools/run_c5.py nograph > $OUT/${R}_c5_run.txt 2> $OUT/trace_c5.err
 cp $(find $OUT/trace_c5 -name "*kernel_stats.csv" | head -1) $OUT/${R}_c5_kernel_stats.csv
