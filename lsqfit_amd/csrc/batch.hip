@@ -6,7 +6,7 @@
 // model, x and the data whitening (1/sdev for the 1x1 rows, W_b per correlated block), and
 // differ in the prior (mean / sdev per fit), the starting point and -- for simulated /
 // bootstrap refits (src/lsqfit/__init__.py:1391-1469,1548-1642) -- the data means.  Per fit the GSL trust/lm/nielsen/scaling/
-// convergence logic of api.hip is restated as small per-fit device kernels (b_decide,
+// convergence logic of lm_driver.hip is restated as small per-fit device kernels (b_decide,
 // b_post); the heavy kernels are the same ones the single-fit path uses, launched with a
 // batch dimension: model kernels (grid.y), TN GEMM (grid.z) for J^T J and the Cholesky
 // panels/updates, the diagonal-block kernel (one workgroup per fit), back substitution.
@@ -28,7 +28,7 @@
 #include "common.h"
 #include "jit.h"
 
-namespace lsqamd_host {   // process-wide recycling of streams and events (api.hip; see fit_state.h)
+namespace lsqamd_host {   // process-wide recycling of streams and events (pool.hip; see fit_state.h)
 hipEvent_t event_take();
 void event_give(hipEvent_t e, int dev = -1);
 hipStream_t stream_take();
@@ -1006,7 +1006,7 @@ int lsqamdb_run(lsqamdb_fits *f, const double *p0, lsqamd_summary *summaries, in
     BHIP(f, hipStreamSynchronize(f->st));
   }
   // Small fits (a compiled formula, <= 12 parameters, <= 4096 uncorrelated rows or <= 256 with covariance blocks): every
-  // fit of the batch is ONE workgroup of ONE launch (jit.hip lsqamd_jit_lmb -- the loop of the single-fit kernel, api.hip
+  // fit of the batch is ONE workgroup of ONE launch (jit.hip lsqamd_jit_lmb -- the loop of the single-fit kernel, lm_driver.hip
   // run_one_launch) instead of ~20 lockstep launches per round.  Any irregular fit sends the whole batch through the
   // lockstep engine below.  LSQAMD_ONE_LAUNCH_FIT=0 disables.
   f->one_launch = false;

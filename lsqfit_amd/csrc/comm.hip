@@ -138,7 +138,7 @@ bool use_rsag() {   // read per call (a getenv next to a 69 MB collective is fre
 
 namespace lsqamd_host {
 
-// sums enqueued on `st` (the handle's stream, or its exchange stream for the grouped exchange of api.hip eval_normal_dev)
+// sums enqueued on `st` (the handle's stream, or its exchange stream for the grouped exchange of eval.hip eval_normal_dev)
 int comm_all_reduce_on(lsqamd_fit *f, hipStream_t st, double *buf, int64_t count) {
   Api &a = api();
   Comm c = (Comm)f->comm;

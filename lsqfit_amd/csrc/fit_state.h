@@ -1,4 +1,4 @@
-// Internal to the host side of the library (api.hip, scipy_methods.hip): the fit handle and the
+// Internal to the host side of the library (api.hip, lm_driver.hip, eval.hip, workspace.hip, pool.hip, scipy_methods.hip, qr.hip): the fit handle and the
 // device-side building blocks the trust-region drivers share.  Not part of the C ABI.
 #pragma once
 #include <cmath>
@@ -15,7 +15,7 @@
 namespace lsqamd_host {
 
 void comm_release(lsqamd_fit *f);                                  // comm.hip
-// process-wide recycling of what a handle needs from the runtime besides its workspace (api.hip): creating and releasing a
+// process-wide recycling of what a handle needs from the runtime besides its workspace (pool.hip): creating and releasing a
 // pinned block or an event costs tens to hundreds of microseconds (hipHostFree waits for the device) -- more than a small fit
 void *pinned_take(size_t bytes, size_t *granted);
 void pinned_give(void *p, size_t granted, int dev = -1);   // dev: the device it was taken on (-1: the current one)
@@ -103,7 +103,7 @@ struct lsqamd_fit {
   void *comm = nullptr;
   int32_t comm_rank = 0, comm_nranks = 1;
   std::string comm_key;            // its entry in the process-wide registry of communicators (comm.hip)
-  // grouped exchange (api.hip eval_normal_dev; LSQAMD_EXCHANGE_GROUPS = G > 1, read at lsqamd_create): the J^T J work list cut
+  // grouped exchange (eval.hip eval_normal_dev; LSQAMD_EXCHANGE_GROUPS = G > 1, read at lsqamd_create): the J^T J work list cut
   // into G groups of tile rows, group g's packed tiles summed over the ranks on `xst` while group g + 1 is computed on `st`
   int32_t xg = 1;                  // groups (1: one launch, one exchange on the step's stream)
   int32_t xg_row[9] = {0};         // tile rows [xg_row[g], xg_row[g + 1]) of group g
@@ -134,14 +134,14 @@ struct lsqamd_fit {
   double f_scale = 1.0;
   std::vector<double> x_scale;
   bool robust() const { return loss != 0 && (opt.trs == LSQAMD_TRS_TRF || opt.trs == LSQAMD_TRS_DOGBOX); }
-  // parameters the residual is linear in (empty: none): variable projection (api.hip iterate_varpro)
+  // parameters the residual is linear in (empty: none): variable projection (lm_driver.hip iterate_varpro)
   std::vector<char> linear;
 
   // LM state (host)
   std::vector<double> hx, hg, hdiag, hdx, hv, hcoln, htmp;
   double chi2 = 0.0, mu = 0.0, delta = 0.0;
   long nu = 2;
-  // plain lm keeps its vectors on the device (api.hip iterate_device): the host mirrors hx / hg /
+  // plain lm keeps its vectors on the device (lm_driver.hip iterate_device): the host mirrors hx / hg /
   // hdiag / hcoln / hv / hdx are refreshed on demand (refresh_mirrors)
   bool dev_lm = false, mirrors_stale = false;
   bool prior_deferred = false;  // eval_normal_dev left the prior's share of g / chi2 to the accept-tail kernel
@@ -169,7 +169,7 @@ struct lsqamd_fit {
   double *fit_block = nullptr;          // that block in DEVICE memory (FitArgs::host): what the kernel writes first, the fallback
   std::vector<double> fit_rec;          // the block as the host verified it (run_one_launch): everything later reads THIS
   bool cov_host_valid = false;    // pin_fit[96 ..] holds the covariance f->cov holds (get_cov serves it without a copy)
-  bool used_one_launch = false;   // the last lsqamd_run was ONE launch (api.hip run_one_launch); lsqamd_debug_flags bit 5
+  bool used_one_launch = false;   // the last lsqamd_run was ONE launch (lm_driver.hip run_one_launch); lsqamd_debug_flags bit 5
   std::vector<hipEvent_t> event_pool;
   size_t pin_bytes = 0;     // size class the pinned block came with (pinned_take)
   // pinned staging arena for small host inputs (api.hip Upload): a setter copies in, queues the upload and returns
@@ -272,10 +272,10 @@ struct Scope {  // HIP-event bracket for one phase
   }
 };
 
-// ---- device-side building blocks (api.hip) ----------------------------------------------------
+// ---- device-side building blocks (eval.hip) ---------------------------------------------------
 // sum count doubles over the ranks of a sharded fit, in place (RCCL communicator or the hook)
 int do_reduce(lsqamd_fit *f, double *buf, int64_t count);
-// (J^T J)^-1 and log det J^T J at the current point: normal equations (api.hip) / CholeskyQR (qr.hip)
+// (J^T J)^-1 and log det J^T J at the current point: normal equations (eval.hip) / CholeskyQR (qr.hip)
 int do_covariance(lsqamd_fit *f);
 int do_covariance_qr(lsqamd_fit *f);
 int covariance_rank_deficient(lsqamd_fit *f);   // rankdef.hip

@@ -264,7 +264,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_f64_kernel(GemmDev g) {
 // colsum_out[(b * splits + split) * colsum_ld + m]: per-split partials, summed in split order by the caller.
 // SIGNAL (with WORKMAP): the work list's 4th word names the entry's exchange group (1-based); when the entry's tile is in its
 // slab the workgroup adds one to done_ctr[group - 1] with release semantics -- a one-wave kernel on another stream of the
-// handle waits for the count of a group's entries (api.hip: the grouped exchange without splitting this launch).
+// handle waits for the count of a group's entries (eval.hip: the grouped exchange without splitting this launch).
 template <bool XTRI, bool WORKMAP, bool CS = false, bool SIGNAL = false>
 __global__ __launch_bounds__(256, 2) void gemm_tn_f64_interior_kernel(GemmDev g) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -1086,7 +1086,7 @@ int64_t syrk_work_count(int64_t P, int32_t splits) {
 
 void syrk_work_fill(int64_t P, int32_t splits, int32_t *out) { (void)syrk_work_fill_rows(P, splits, 0, (int)((P + BM - 1) / BM), out); }
 
-// the same list for the tile rows [row0, row1) only (the exchange groups of a sharded fit, api.hip eval_normal_dev: one launch
+// the same list for the tile rows [row0, row1) only (the exchange groups of a sharded fit, eval.hip eval_normal_dev: one launch
 // per group of tile rows, so that a group's packed tiles can be on their way to the other ranks while the next group is being
 // computed); returns the number of entries.  Same ordering rules as the full list: 8 x 8 patches of tiles for the L2, one
 // eighth of the list per XCD, a chunk's diagonal tiles last.

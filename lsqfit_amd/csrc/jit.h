@@ -67,7 +67,7 @@ struct FitArgs {
   // pub != null: device-visible pinned HOST block the finished record block is published to for a host that polls instead of
   // waiting for the stream.  Stores to host memory land in no particular order, so the block is self-verifying: words
   // [0, fit_host_cov(P) + P * P) are the record block, except [23] = fit_checksum over the others seeded with seq, and
-  // [16] = fit_flag(reason, info, nit, seq), the word the host waits for (api.hip run_one_launch)
+  // [16] = fit_flag(reason, info, nit, seq), the word the host waits for (lm_driver.hip run_one_launch)
   unsigned long long *pub, seq;
 };
 // the self-verification of a published record block (host side; the kernel's twin is at the end of lm_fit in jit.hip)

@@ -1,6 +1,6 @@
 // scipy_least_squares' three methods on the device's normal equations:
 // Trust Region Reflective and dogbox (box bounds), MINPACK's lmder.  Host-side step logic only --
-// every O(N P), O(P^2) and O(P^3) operation is one of the building blocks of api.hip
+// every O(N P), O(P^2) and O(P^3) operation is one of the building blocks of eval.hip
 // (fit_state.h); the reference reaches these methods through src/lsqfit/_scipy.py:115-181.
 #include "fit_state.h"
 

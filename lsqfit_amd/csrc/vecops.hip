@@ -787,7 +787,7 @@ __device__ __forceinline__ void lm_publish(double *st) {
   // called by ONE thread after it has written the record.  Stores to host memory become visible to the CPU in no
   // particular order -- a system-scope fence between two of them does not help (measured on the one-launch fit's larger
   // block, jit.hip lm_fit) -- so the mirror is self-verifying: word LMS_CHECK carries lm_record_checksum of the other
-  // fifteen, the new sequence number among them; the host believes a snapshot only when the sum fits (api.hip wait_record).
+  // fifteen, the new sequence number among them; the host believes a snapshot only when the sum fits (lm_driver.hip wait_record).
   const long long hp = __double_as_longlong(st[LMS_HOSTPTR]);
   const double seq = st[LMS_SEQ] + 1.0;
   st[LMS_SEQ] = seq;

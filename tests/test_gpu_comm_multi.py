@@ -182,7 +182,7 @@ def test_rsag_and_allreduce_forms_agree_bit_for_bit(runs):
 def test_grouped_exchange_is_bit_identical(case, world, groups, runs):
     """LSQAMD_EXCHANGE_GROUPS = G: the J^T J tiles in G groups of tile rows, group g's packed tiles summed over the ranks
     on the handle's exchange stream while the rest of the product is computed, the step's stream waiting for the last
-    event before the damped matrix is built (api.hip eval_normal_dev).  Two forms: ONE product launch whose workgroups count
+    event before the damped matrix is built (eval.hip eval_normal_dev).  Two forms: ONE product launch whose workgroups count
     a group's finished entries, a one-wave kernel on the exchange stream waiting for the count ('G', the default); one
     product launch per group ('Gs', LSQAMD_EXCHANGE_MODE=split).  Every element is still the same sum of the same split-K
     slabs and the stand-in sums ranks in rank order whatever the slice: fits must be the same BITS as with one exchange, on

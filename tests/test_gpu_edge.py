@@ -204,7 +204,7 @@ def test_query_devices_reports_the_mi355x():
 def test_cosine_model_range_flag_at_size(amd, scale):
     """From a few million cosines per evaluation on, the model kernels run as a pair -- one without far-range trig
     code, one with -- and a device flag computed from the frequencies leaves exactly one of them with work
-    (api.hip residual_vector_launch, model.hip trig_range_kernel).  Both sides of the flag against numpy."""
+    (eval.hip residual_vector_launch, model.hip trig_range_kernel).  Both sides of the flag against numpy."""
     from lsqfit_amd import synth
     d = synth.make_cosmix(N=8192, P=1024, seed=12, block=256, prior_corr=False)
     wh = amd.Whitening(d['ymean'], d['yerr'], *d['prior'])

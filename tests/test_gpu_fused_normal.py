@@ -1,5 +1,5 @@
 """-m gpu: few parameters, many rows -- the normal equations formed straight from the compiled formula's registers
-(jit.hip lsqamd_jit_nrm: J^T J, J^T f, chi2 per workgroup, the Jacobian never written; api.hip eval_normal_dev).
+(jit.hip lsqamd_jit_nrm: J^T J, J^T f, chi2 per workgroup, the Jacobian never written; eval.hip eval_normal_dev).
 The fit must equal the oracle's and the unfused device path's; whatever reads the Jacobian afterwards (fit.J,
 fit.residuals, the QR-grade covariance, fit.p sensitivities) must find it (ensure_J)."""
 import os

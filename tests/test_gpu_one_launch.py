@@ -1,4 +1,4 @@
-"""-m gpu: a whole small fit in ONE launch (jit.hip lsqamd_jit_lm, api.hip run_one_launch) -- compiled formula, at most a
+"""-m gpu: a whole small fit in ONE launch (jit.hip lsqamd_jit_lm, lm_driver.hip run_one_launch) -- compiled formula, at most a
 few dozen parameters, a few thousand uncorrelated rows (or a few hundred correlated ones), plain lm.  Every case is checked
 (a) against the ORACLE (oracle/fit.py: the restated gsl_multifit driver, src/lsqfit/_gsl.pyx:676-706, dual-number Jacobians)
 at the north-star tolerance of 1e-6 -- parameters, chi2, covariance, logGBF, iteration count and stopping criterion -- with
@@ -482,7 +482,7 @@ def test_handoff_modes_agree_bit_for_bit(amd, zero_copy, monkeypatch):
 
 
 def test_general_small_path_record_is_verified(amd, monkeypatch):
-    """The general path's 16-word LM record is polled from pinned memory too (api.hip wait_record): two hundred half steps with the
+    """The general path's 16-word LM record is polled from pinned memory too (lm_driver.hip wait_record): two hundred half steps with the
     audit on, both modes, same trajectory."""
     monkeypatch.setenv('LSQAMD_ONE_LAUNCH_FIT', '0')
     x, y, sd, pt = curve(N=2000, seed=5)

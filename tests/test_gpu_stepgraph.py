@@ -1,4 +1,4 @@
-"""-m gpu: the device-resident LM step replayed from captured graphs (api.hip run_half): the trial
+"""-m gpu: the device-resident LM step replayed from captured graphs (lm_driver.hip run_half): the trial
 (factor, solve, trial point, residual, decision, 128-byte read-back) and the accepted branch
 (Jacobian, normal equations, scaling, convergence test) are each captured once per parameter-buffer
 parity and replayed.  Same kernels, same arguments: the fit must be bit-identical to the eager one."""

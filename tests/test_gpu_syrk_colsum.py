@@ -1,5 +1,5 @@
 """-m gpu: J^T f and chi2 formed by the diagonal tiles of the split-K J^T J launch (gemm_tn_f64.hip
-gemm_tn_f64_interior_kernel<false, true, true>; api.hip eval_normal_dev) instead of a second pass over J.
+gemm_tn_f64_interior_kernel<false, true, true>; eval.hip eval_normal_dev) instead of a second pass over J.
 Checked against the separate pass (LSQAMD_SYRK_COLSUM=0, read per call) and against numpy on the
 Jacobian the device hands back; J^T J itself must not change by a bit."""
 import numpy as np

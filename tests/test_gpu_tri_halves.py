@@ -1,6 +1,6 @@
 """-m gpu: whitening product of ONE large dense block (BASELINE config 3's shape: a fully correlated data set).
 With few long tile rows the triangular product runs both halves of every tile row's K-range as separate
-workgroups (gemm_tn_f64.hip gemm_tn_wants_tri_halves; api.hip whiten_jacobian adds the scratch slab back).
+workgroups (gemm_tn_f64.hip gemm_tn_wants_tri_halves; eval.hip whiten_jacobian adds the scratch slab back).
 Checked against the one-workgroup-per-row-pair launch (LSQAMD_TRI_HALVES=0, read per call)."""
 import numpy as np
 import pytest

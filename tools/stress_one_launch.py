@@ -4,7 +4,7 @@
 
 Repeats the sequence of tests/test_gpu_one_launch.py that went red on the round-3 driver box (nine prior x scaler fits
 through both routes, then the maxit = 3 fit) and counts every disagreement instead of stopping at the first.  Run it
-with LSQAMD_VERIFY_HANDOFF=1 (api.hip run_one_launch prints every word that changed between "flag seen" and "stream
+with LSQAMD_VERIFY_HANDOFF=1 (lm_driver.hip run_one_launch prints every word that changed between "flag seen" and "stream
 drained") and with LSQAMD_POISON_PINNED=1."""
 import os
 import sys
