@@ -382,6 +382,12 @@ int lsqamd_op_gemm_tn(void *stream, int64_t M, int64_t N, int64_t K, double alph
 int lsqamd_op_potrf_upper(void *stream, double *A, int64_t n, int64_t lda, int64_t n_cols,
                           double *work, size_t work_bytes, int32_t *dev_info);
 size_t lsqamd_op_potrf_work_bytes(int64_t n);
+/* the batched engine's symmetric product on its packed 128 x 128 tiles (dogleg family): y[b] = A[b] u[b], quad[b] = u[b]^T A[b] u[b]
+ * for the fits with active[b] != 0 (the others' outputs are left alone).  A[n_fits][P][P] dense row-major, of which only the
+ * upper triangle is read; u, y [n_fits][P]; quad [n_fits]; device pointers.  Deterministic (no floating-point atomics).
+ * Allocates its scratch and waits for the stream: a test entry point, not for capture. */
+int lsqamdb_op_symv_packed(void *stream, int64_t P, int32_t n_fits, const double *A, const double *u, const int32_t *active,
+                           double *y, double *quad);
 /* host arithmetic of the rank-deficient covariance (rankdef.hip; what lsqamd_run / lsqamd_finish fall back to when
  * J^T J has no Cholesky factor at the end point): G[n*n] = J^T J, n_rows = rows of J; scipy_form 0: gsl_multifit_nlinear_covar's
  * pivoted recipe (_gsl.pyx:704-706), 1: the thresholded pseudo-inverse of _scipy.py:170-175.  Host pointers, no GPU. */
@@ -433,7 +439,10 @@ int64_t lsqamd_nf(const lsqamd_fit *fit);                         /* nchiv (__in
  * different (diagonal) priors and starting points -- advanced in lockstep with all LM state
  * on the device and one round of kernels captured in a hipGraph.  Device counterpart of the
  * Python loop of whole fits in lsqfit.empbayes_fit (src/lsqfit/_extras.py:153-174); per fit
- * the driver semantics are those of lsqamd_run. */
+ * the driver semantics are those of lsqamd_run.  lsqamdb_set_options accepts options.trs = LSQAMD_TRS_LM, _DOGLEG, _DDOGLEG
+ * and _SUBSPACE2D (the dogleg family recomputes its two legs -- one symmetric product, one factorisation -- only for the
+ * fits whose trial was accepted; a rejected trial costs a residual); _LMACCEL and the scipy methods: LSQAMD_EUNSUPPORTED.
+ * Batches of small fits run as one launch with plain LM only; with another method they take the lockstep rounds. */
 typedef struct lsqamdb_fits lsqamdb_fits;
 size_t lsqamdb_workspace_bytes(const lsqamd_config *cfg, int32_t n_fits);
 int lsqamdb_create(const lsqamd_config *cfg, int32_t n_fits, void *dev_workspace, size_t workspace_bytes,

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from .fit import gammaQ
-from .fitter import _SCALERS, normalize_tol
+from .fitter import _ALGS, _SCALERS, normalize_tol
 from .models import MODEL_IDENTITY, MODEL_TAPE
 
 
@@ -162,9 +162,13 @@ class BatchedFits:
         self._check(self.lib.lsqamdb_set_priors(self.h, _lib.dptr(mean), _lib.anyptr(prec)), 'set_priors')
 
     def run(self, p0=None, tol=1e-8, maxit=1000, scaler='more', factor_up=3.0, factor_down=2.0,
-            use_graph=True, covariance=True):
+            use_graph=True, covariance=True, alg='lm'):
         """-> dict of arrays: pmean[B,P], chi2, dof, Q, logGBF, nit, stopping_criterion, status,
-        nfev (+ psdev[B,P] and cov(b) when ``covariance``)."""
+        nfev (+ psdev[B,P] and cov(b) when ``covariance``).  ``alg``: 'lm', 'dogleg', 'ddogleg' or 'subspace2D'
+        (``nonlinear_fit``'s names, _gsl.pyx:622-635); 'lmaccel' is refused by the library (it needs one more residual
+        evaluation per trial).  Small batches that plain LM runs as one launch take the lockstep rounds with the others."""
+        if alg not in _ALGS:
+            raise ValueError('unknown alg %r: the batched engine runs lm, dogleg, ddogleg and subspace2D' % (alg,))
         B, P = self.B, self.P
         if p0 is None and not self.has_prior:
             raise ValueError('neither p0 nor prior is specified')
@@ -175,7 +179,7 @@ class BatchedFits:
         p0 = np.ascontiguousarray(np.broadcast_to(np.asarray(p0, np.float64), (B, P)))
         xtol, gtol, ftol = normalize_tol(tol)
         opt = _lib.Options(xtol=xtol, gtol=gtol, ftol=ftol, maxit=int(maxit), scaler=_SCALERS[scaler], solver=0,
-                           trs=0, factor_up=factor_up, factor_down=factor_down, avmax=0.75)
+                           trs=_ALGS[alg], factor_up=factor_up, factor_down=factor_down, avmax=0.75)
         self._check(self.lib.lsqamdb_set_options(self.h, C.byref(opt)), 'set_options')
         summ = (_lib.Summary * B)()
         t0 = time.perf_counter()

@@ -17,6 +17,10 @@
 //   -> Jacobian, J^T J, J^T f, chi2 at the fit's current x (unchanged if it rejected)
 //   -> post (scaling update, niter, convergence tests, retire finished fits).
 // Fits that have finished are masked out of every kernel through `active[b]`.
+//
+// opt.trs = DOGLEG / DDOGLEG / SUBSPACE2D runs another round (round_trs; the branch is taken on the host, LM's launches are
+// untouched): step for the current trust radius from the two legs -> residual -> decide (rho, delta) -> commit -> normal
+// equations of the fits that moved -> post -> new legs for those fits (legs_all).  Kernels: batch_trs.hip.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -25,7 +29,7 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "batch.h"
 #include "jit.h"
 
 namespace lsqamd_host {   // process-wide recycling of streams and events (pool.hip; see fit_state.h)
@@ -36,43 +40,6 @@ void stream_give(hipStream_t s, int dev = -1);
 }  // namespace lsqamd_host
 
 namespace lsqamd {
-
-constexpr int TBK = 128;  // packed tile edge (vecops.hip)
-
-__device__ __forceinline__ double bsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-  v = bsum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-__device__ __forceinline__ double block_max(double v, double *sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
-}
-
-__device__ __forceinline__ int64_t pk_diag(int64_t j, int64_t T) {  // packed offset of A[j][j]
-  const int64_t tm = j / TBK, r = j % TBK;
-  return (tm * T - tm * (tm - 1) / 2) * TBK * TBK + r * TBK + r;
-}
-
-struct BState {  // per-fit device scalars
-  double *mu, *chi2, *chi2t, *vg, *dv2;
-  int32_t *nu, *bad, *iter, *nit, *info, *status, *active, *accepted, *enoprog, *cholinfo, *nfev, *njev;
-  int32_t *n_active;
-  int32_t *moved;   // active and accepted this round: the only fits whose normal equations change
-};
 
 // ---- slabs -> packed tiles ---------------------------------------------------------------
 __global__ __launch_bounds__(256) void b_finalize_pack_kernel(const double *slabs, int32_t splits,
@@ -527,6 +494,7 @@ struct lsqamdb_fits {
   int32_t *syrk_map = nullptr;
   int32_t syrk_nwork = 0;
   BState s;
+  BTrs t;                    // the dogleg family's per-fit state (batch_trs.hip)
   bool have_x = false, have_data = false, have_prior = false, have_tape = false, ran = false, have_cov = false;
   hipGraph_t graph = nullptr;
   hipGraphExec_t gexec = nullptr;
@@ -645,6 +613,12 @@ size_t carve_b(lsqamdb_fits *f, void *ws, bool dry) {
   f->s.moved = cv.take<int32_t>(B);
   f->syrk_nwork = (int32_t)syrk_work_count(P, f->splits);
   f->syrk_map = cv.take<int32_t>(4 * (int64_t)f->syrk_nwork);
+  // dogleg family (after everything plain LM uses: its layout does not move)
+  f->t.rec = cv.take<double>(B * TR_COUNT);
+  f->t.w = cv.take<double>(B * P); f->t.aw = cv.take<double>(B * P);
+  f->t.dx_sd = cv.take<double>(B * P); f->t.dx_gn = cv.take<double>(B * P);
+  f->t.part = cv.take<double>(B * symv_packed_partials(P));
+  f->t.gn_failed = cv.take<int32_t>(B); f->t.lmask = cv.take<int32_t>(B);
   return cv.off;
 }
 
@@ -751,8 +725,28 @@ int normal_all(lsqamdb_fits *f, const int32_t *mask) {
   return 0;
 }
 
-int round_all(lsqamdb_fits *f) {
+// residual and chi2 (+ prior term) of every active fit at its trial point
+int trial_chi2_all(lsqamdb_fits *f) {
   const int64_t P = f->P, N = f->N, B = f->B;
+  ModelArgs m = model_args_b(f, f->pxt);
+  m.out_stride = N;
+  BHIP(f, launch_residual_ex(f->st, m, f->r, f->cfg.n_blocks > 0 ? f->r_raw : nullptr));
+  if (f->cfg.n_blocks > 0)
+    BHIP(f, launch_block_whiten_vec(f->st, f->wt, f->blk_row0, f->blk_size, f->blk_woff, f->cfg.n_blocks,
+                                    f->cfg.max_block, f->r_raw, f->r, (int32_t)B, N, f->s.active));
+  hipLaunchKernelGGL(b_sumsq_stage1, dim3((unsigned)f->nrparts, (unsigned)B), dim3(256), 0, f->st, f->r, N, N,
+                     f->spart, f->nrparts, f->s.active);
+  const bool dense_prior = f->cfg.has_prior && f->cfg.prior_dense;
+  if (dense_prior)
+    hipLaunchKernelGGL(b_prior_vec_dense_kernel, dim3((unsigned)((P + 3) / 4), (unsigned)B), dim3(256), 0, f->st,
+                       P, f->pprec, f->pmean, f->pxt, f->ptvec, f->s.active);
+  hipLaunchKernelGGL(b_sumsq_stage2, dim3((unsigned)B), dim3(256), 0, f->st, f->spart, f->nrparts, P, f->pprec,
+                     f->pmean, f->pxt, f->cfg.has_prior, dense_prior ? f->ptvec : nullptr, f->s);
+  return 0;
+}
+
+int round_all(lsqamdb_fits *f) {
+  const int64_t P = f->P, B = f->B;
   const int64_t red_stride = f->npk + P + 1, m_stride = P * f->ldm, w_stride = f->nblk * 128 * 128;
   const unsigned ntile = (unsigned)(f->T * (f->T + 1) / 2);
   hipLaunchKernelGGL(b_build_damped_kernel, dim3(ntile, 16, (unsigned)B), dim3(256), 0, f->st, f->red,
@@ -775,25 +769,13 @@ int round_all(lsqamdb_fits *f) {
                                   2 * P, f->s.active));
   hipLaunchKernelGGL(b_trial_kernel, dim3((unsigned)B), dim3(256), 0, f->st, P, f->yv, 2 * P, f->px,
                      f->red + f->npk, red_stride, f->diag, f->dx, f->pxt, f->s);
-  ModelArgs m = model_args_b(f, f->pxt);
-  m.out_stride = N;
-  BHIP(f, launch_residual_ex(f->st, m, f->r, f->cfg.n_blocks > 0 ? f->r_raw : nullptr));
-  if (f->cfg.n_blocks > 0)
-    BHIP(f, launch_block_whiten_vec(f->st, f->wt, f->blk_row0, f->blk_size, f->blk_woff, f->cfg.n_blocks,
-                                    f->cfg.max_block, f->r_raw, f->r, (int32_t)B, N, f->s.active));
-  hipLaunchKernelGGL(b_sumsq_stage1, dim3((unsigned)f->nrparts, (unsigned)B), dim3(256), 0, f->st, f->r, N, N,
-                     f->spart, f->nrparts, f->s.active);
-  const bool dense_prior = f->cfg.has_prior && f->cfg.prior_dense;
-  if (dense_prior)
-    hipLaunchKernelGGL(b_prior_vec_dense_kernel, dim3((unsigned)((P + 3) / 4), (unsigned)B), dim3(256), 0, f->st,
-                       P, f->pprec, f->pmean, f->pxt, f->ptvec, f->s.active);
-  hipLaunchKernelGGL(b_sumsq_stage2, dim3((unsigned)B), dim3(256), 0, f->st, f->spart, f->nrparts, P, f->pprec,
-                     f->pmean, f->pxt, f->cfg.has_prior, dense_prior ? f->ptvec : nullptr, f->s);
+  int rc = trial_chi2_all(f);
+  if (rc) return rc;
   hipLaunchKernelGGL(b_decide_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, f->st, (int)B,
                      f->opt.factor_up, f->opt.factor_down, f->s);
   hipLaunchKernelGGL(b_commit_kernel, dim3((unsigned)((P + 255) / 256), (unsigned)B), dim3(256), 0, f->st, P,
                      f->px, f->pxt, f->s);
-  int rc = normal_all(f, f->s.moved);
+  rc = normal_all(f, f->s.moved);
   if (rc) return rc;
   hipLaunchKernelGGL(b_post_kernel, dim3((unsigned)B), dim3(256), 0, f->st, P, f->T, f->red, red_stride,
                      f->red + f->npk, red_stride, f->diag, f->px, f->dx, f->opt.scaler, f->opt.xtol, f->opt.gtol,
@@ -802,6 +784,57 @@ int round_all(lsqamdb_fits *f) {
   BHIP(f, hipGetLastError());
   return 0;
 }
+
+// ---- the dogleg family (opt.trs = DOGLEG / DDOGLEG / SUBSPACE2D; kernels in batch_trs.hip) ------------------------------
+// The two legs of every fit flagged in `mask` at its current (A, g, D): w = D^-2 g, ONE symmetric product for w^T A w, the
+// Gauss-Newton point from the undamped normal equations (the same build / factorisation / back substitution as an LM trial,
+// with mu = 0), then the scalars the step kernel works from.
+int legs_all(lsqamdb_fits *f, const int32_t *mask) {
+  const int64_t P = f->P, B = f->B;
+  const int64_t red_stride = f->npk + P + 1, m_stride = P * f->ldm, w_stride = f->nblk * 128 * 128;
+  const unsigned ntile = (unsigned)(f->T * (f->T + 1) / 2);
+  const double *gvec = f->red + f->npk;
+  BHIP(f, launch_trs_grad(f->st, P, (int32_t)B, gvec, red_stride, f->diag, f->t, mask));
+  BHIP(f, launch_symv_packed(f->st, f->red, red_stride, P, (int32_t)B, f->t.w, P, f->t.part, f->t.aw, P, f->t.rec + TR_WAW,
+                             TR_COUNT, mask));
+  hipLaunchKernelGGL(b_build_damped_kernel, dim3(ntile, 16, (unsigned)B), dim3(256), 0, f->st, f->red, red_stride, P, f->T,
+                     f->ldm, f->s.mu, f->diag, gvec, red_stride, f->M, m_stride, mask, 0);
+  BHIP(f, potrf_upper_batched(f->st, f->M, P, f->ldm, f->ncols_aug, f->chol_work, f->s.cholinfo, (int32_t)B, m_stride,
+                              w_stride, mask));
+  hipLaunchKernelGGL(b_extract_y_kernel, dim3((unsigned)((P + 255) / 256), (unsigned)B), dim3(256), 0, f->st, f->M, m_stride,
+                     f->ldm, P, f->yv, 2 * P, mask);
+  BHIP(f, backsolve_upper_batched(f->st, f->M, P, f->ldm, f->chol_work, f->yv, (int32_t)B, m_stride, w_stride, 2 * P, mask));
+  BHIP(f, launch_trs_legs(f->st, P, (int32_t)B, f->opt.trs, gvec, red_stride, f->diag, f->yv + P, 2 * P, f->s.cholinfo, f->t,
+                          mask));
+  return 0;
+}
+
+// One round of the family: the step for the current delta -> residual and chi2 there -> rho, delta, accept / reject ->
+// the accepted fits move, get new normal equations, the scaling update and the convergence tests (b_post_kernel, as in LM)
+// -> new legs for the fits that moved and go on.  A fit that rejected keeps its legs: no product, no factorisation.
+int round_trs(lsqamdb_fits *f) {
+  const int64_t P = f->P, B = f->B;
+  const int64_t red_stride = f->npk + P + 1;
+  BHIP(f, launch_trs_step(f->st, P, (int32_t)B, f->opt.trs, f->px, f->pxt, f->dx, f->t, f->s.active));
+  int rc = trial_chi2_all(f);
+  if (rc) return rc;
+  BHIP(f, launch_trs_decide(f->st, (int32_t)B, f->opt.factor_up, f->opt.factor_down, f->s, f->t));
+  hipLaunchKernelGGL(b_commit_kernel, dim3((unsigned)((P + 255) / 256), (unsigned)B), dim3(256), 0, f->st, P,
+                     f->px, f->pxt, f->s);
+  rc = normal_all(f, f->s.moved);
+  if (rc) return rc;
+  hipLaunchKernelGGL(b_post_kernel, dim3((unsigned)B), dim3(256), 0, f->st, P, f->T, f->red, red_stride,
+                     f->red + f->npk, red_stride, f->diag, f->px, f->dx, f->opt.scaler, f->opt.xtol, f->opt.gtol,
+                     f->opt.maxit, f->s);
+  BHIP(f, launch_trs_mask(f->st, (int32_t)B, f->s, f->t));
+  rc = legs_all(f, f->t.lmask);
+  if (rc) return rc;
+  hipLaunchKernelGGL(b_count_kernel, dim3(1), dim3(256), 0, f->st, (int)B, f->s);
+  BHIP(f, hipGetLastError());
+  return 0;
+}
+
+int round_any(lsqamdb_fits *f) { return f->opt.trs == LSQAMD_TRS_LM ? round_all(f) : round_trs(f); }
 
 }  // namespace
 
@@ -979,7 +1012,8 @@ int lsqamdb_set_options(lsqamdb_fits *f, const lsqamd_options *opt) try {
   if (!f || !opt) return LSQAMD_EINVAL;
   if (opt->xtol < 0 || opt->gtol < 0 || opt->maxit < 0 || opt->scaler < 0 || opt->scaler > LSQAMD_SCALE_MARQUARDT)
     BFAIL(f, LSQAMD_EINVAL, "set_options: bad value");
-  if (opt->trs != LSQAMD_TRS_LM) BFAIL(f, LSQAMD_EUNSUPPORTED, "set_options: the batched engine runs alg='lm' only");
+  if (opt->trs != LSQAMD_TRS_LM && opt->trs != LSQAMD_TRS_DOGLEG && opt->trs != LSQAMD_TRS_DDOGLEG && opt->trs != LSQAMD_TRS_SUBSPACE2D)
+    BFAIL(f, LSQAMD_EUNSUPPORTED, "set_options: the batched engine runs alg='lm', 'dogleg', 'ddogleg' and 'subspace2D' only");
   f->opt = *opt;
   return 0;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
@@ -1066,6 +1100,11 @@ int lsqamdb_run(lsqamdb_fits *f, const double *p0, lsqamd_summary *summaries, in
   if (rc) return rc;
   hipLaunchKernelGGL(b_init_kernel, dim3((unsigned)B), dim3(256), 0, f->st, P, f->T, f->red, f->npk + P + 1,
                      f->red + f->npk, f->npk + P + 1, f->diag, f->opt.scaler, f->s);
+  if (f->opt.trs != LSQAMD_TRS_LM) {   // the family's trust radius and the legs at p0
+    BHIP(f, launch_trs_init(f->st, P, (int32_t)B, f->diag, f->px, f->t));
+    rc = legs_all(f, f->s.active);
+    if (rc) return rc;
+  }
   f->rounds = 0;
   f->graph_used = 0;
   // kernel arguments (tolerances, maxit, factors) are baked into graph nodes: re-capture per run
@@ -1078,7 +1117,7 @@ int lsqamdb_run(lsqamdb_fits *f, const double *p0, lsqamd_summary *summaries, in
       if (!f->gexec) {
         hipError_t e = hipStreamBeginCapture(f->st, hipStreamCaptureModeThreadLocal);
         if (e == hipSuccess) {
-          rc = round_all(f);
+          rc = round_any(f);
           hipGraph_t gr = nullptr;
           e = hipStreamEndCapture(f->st, &gr);
           // a capture another thread's activity invalidated makes the captured launches fail too: that is a failed CAPTURE
@@ -1102,11 +1141,11 @@ int lsqamdb_run(lsqamdb_fits *f, const double *p0, lsqamd_summary *summaries, in
         BHIP(f, hipGraphLaunch(f->gexec, f->st));
         f->graph_used += 1;
       } else {
-        rc = round_all(f);
+        rc = round_any(f);
         if (rc) return rc;
       }
     } else {
-      rc = round_all(f);
+      rc = round_any(f);
       if (rc) return rc;
     }
     f->rounds += 1;
@@ -1224,6 +1263,26 @@ int lsqamdb_get_cov_all(lsqamdb_fits *f, double *out, size_t cap) try {
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
 
 int32_t lsqamdb_rounds(const lsqamdb_fits *f) { return f ? f->rounds : -1; }
+
+/* the symmetric product of the dogleg family on its own (tests): A[n_fits][P][P] dense, row-major, only its upper triangle read;
+ * packs it into the engine's tiles and runs the production kernels.  Scratch is allocated and freed here: not capturable. */
+int lsqamdb_op_symv_packed(void *stream, int64_t P, int32_t n_fits, const double *A, const double *u, const int32_t *active,
+                           double *y, double *quad) try {
+  if (P < 1 || n_fits < 1 || !A || !u || !active || !y || !quad) return LSQAMD_EINVAL;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t npk = packed_doubles(P), npart = symv_packed_partials(P);
+  double *scratch = nullptr;
+  if (hipMalloc(reinterpret_cast<void **>(&scratch), sizeof(double) * (size_t)(n_fits * (npk + npart))) != hipSuccess) {
+    (void)hipGetLastError();
+    return LSQAMD_ENOMEM;
+  }
+  double *apk = scratch, *part = scratch + (int64_t)n_fits * npk;
+  hipError_t e = launch_pack_dense(st, A, P, P * P, P, n_fits, apk, npk);
+  if (e == hipSuccess) e = launch_symv_packed(st, apk, npk, P, n_fits, u, P, part, y, P, quad, 1, active);
+  const hipError_t e2 = hipStreamSynchronize(st);
+  (void)hipFree(scratch);
+  return (e == hipSuccess && e2 == hipSuccess) ? 0 : LSQAMD_EHIP;
+} LSQAMD_ABI_CATCH(return lsqamd::abi_exception(nullptr);)
 
 int lsqamdb_timing_enable(lsqamdb_fits *f, int32_t on) try {
   if (!f) return LSQAMD_EINVAL;

@@ -6,7 +6,8 @@ The reference loops over whole Python fits, one per copy of the data.  Every cop
 has the structure of the original fit (same model, x, covariance, whitening; only
 the data means -- and optionally the prior means -- change), so here the copies run
 as ONE lockstep batch on the device (:class:`lsqfit_amd.BatchedFits`, C ABI
-``lsqamdb_*``): correlated data blocks and a correlated (dense) prior are shared by
+``lsqamdb_*``; plain LM and the dogleg family -- ``alg='dogleg'``, ``'ddogleg'``,
+``'subspace2D'`` -- with the original fit's ``alg``): correlated data blocks and a correlated (dense) prior are shared by
 the copies, data and prior MEANS are per copy.
 
 Random numbers: ``numpy.random.Generator(PCG64(seed))`` (the reference draws from
@@ -65,15 +66,16 @@ class ResampledFits(dict):
 
 
 _BATCHED_ARGS = {'alg', 'scaler', 'factor_up', 'factor_down', 'solver', 'avmax'}
+_BATCHED_ALGS = {'lm', 'dogleg', 'ddogleg', 'subspace2D'}
 
 
 def _batchable(fit):
-    """the lockstep engine runs plain LM: a fit made with another fitter, another algorithm, a robust loss, bounds or
+    """the lockstep engine runs plain LM and the dogleg family: a fit made with another fitter, with lmaccel, a robust loss, bounds or
     ``x_scale`` is refitted copy by copy with ITS fitter and arguments (src/lsqfit/__init__.py:1457-1459,:1603-1604)"""
     args = getattr(fit, 'fitterargs', {})
     # the batch engine factors the normal equations (solver = cholesky) with the default avmax: a fit made with solver='qr' or
     # another avmax keeps ITS arguments, i.e. goes copy by copy; scaler / factor_up / factor_down are forwarded (refit)
-    return (fit.fitter == 'mi355x_lm' and args.get('alg', 'lm') == 'lm' and set(args) <= _BATCHED_ARGS and not getattr(fit, 'linear', None)
+    return (fit.fitter == 'mi355x_lm' and args.get('alg', 'lm') in _BATCHED_ALGS and set(args) <= _BATCHED_ARGS and not getattr(fit, 'linear', None)
             and args.get('solver', 'cholesky') == 'cholesky' and float(args.get('avmax', 0.75)) == 0.75)
 
 
@@ -150,7 +152,7 @@ def refit(fit, ymeans, prior_means, p0, tol=None, maxit=None, covariance=True):
                      prior_logdet=(wh.logdet - wh.logdet_data) if dense else None, rows_permuted=perm is not None)
     args = getattr(fit, 'fitterargs', {})      # the copies are fitted with the original fit's arguments (src/lsqfit/__init__.py:1457-1459)
     out = bf.run(p0=p0, tol=tol, maxit=maxit, covariance=covariance, scaler=args.get('scaler', 'more'),
-                 factor_up=float(args.get('factor_up', 3.0)), factor_down=float(args.get('factor_down', 2.0)))
+                 factor_up=float(args.get('factor_up', 3.0)), factor_down=float(args.get('factor_down', 2.0)), alg=args.get('alg', 'lm'))
     bf.close()
     res = ResampledFits(out)
     res['engine'] = 'batched'

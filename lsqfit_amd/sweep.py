@@ -28,7 +28,8 @@ from .fit import nonlinear_fit
 
 SweepFit = namedtuple('SweepFit', 'width pmean psdev chi2 dof Q logGBF nit stopping_criterion')
 
-_BATCHABLE = {'data', 'model', 'prior', 'p0', 'tol', 'maxit', 'svdcut'}
+_BATCHABLE = {'data', 'model', 'prior', 'p0', 'tol', 'maxit', 'svdcut', 'alg'}
+_BATCH_ALGS = {'lm', 'dogleg', 'ddogleg', 'subspace2D'}      # what the lockstep engine runs (BatchedFits.run)
 
 
 def _same_x(a, b):
@@ -131,7 +132,9 @@ class EvidenceSurface:
                 return None
             if a['model'] is not a0['model'] or not all(_same(u, v) for u, v in zip(a['data'], a0['data'])):
                 return None
-            if any(a.get(k) != a0.get(k) for k in ('tol', 'maxit', 'svdcut')):
+            if any(a.get(k) != a0.get(k) for k in ('tol', 'maxit', 'svdcut', 'alg')):
+                return None
+            if a.get('alg', 'lm') not in _BATCH_ALGS:
                 return None
             pm, pe = a['prior']
             if hasattr(pe, 'keys'):
@@ -143,7 +146,7 @@ class EvidenceSurface:
         eng = self._engine_for(a0, len(items))
         eng.set_priors(np.array([p[0] for p in pri]), np.array([p[1] for p in pri]))
         p0 = self.warm if self.warm is not None else a0.get('p0')
-        kw = {k: a0[k] for k in ('tol', 'maxit') if a0.get(k) is not None}
+        kw = {k: a0[k] for k in ('tol', 'maxit', 'alg') if a0.get(k) is not None}
         out = eng.run(p0=p0, **kw)
         self.nbatches += 1
         vals = -np.asarray(out['logGBF'], float) - np.array([pl for _, pl in items])
@@ -240,7 +243,7 @@ def prior_width_sweep(*args, p0=None, **runkw):
     """``prior_width_sweep(data, model, prior_mean, widths)``: fit the same data under the priors
     ``prior_mean +- widths[j]`` (each width a scalar or a P-vector) as ONE lockstep batch on the device.
     -> [SweepFit] in the order of ``widths`` (a namedtuple: width pmean psdev chi2 dof Q logGBF nit
-    stopping_criterion).  Round 1's form ``prior_width_sweep(problem, data, model, prior_mean, widths)`` -- a
+    stopping_criterion).  Run options (``tol``, ``maxit``, ``alg='dogleg'`` ...) go to :meth:`BatchedFits.run`.  Round 1's form ``prior_width_sweep(problem, data, model, prior_mean, widths)`` -- a
     resident ``DeviceProblem`` first, a list of fit objects back -- is still accepted: the problem is not
     needed any more and is ignored; the return value is the list of SweepFit records either way."""
     from .batched import BatchedFits
