@@ -30,14 +30,7 @@
 #include <vector>
 
 #include "batch.h"
-#include "jit.h"
-
-namespace lsqamd_host {   // process-wide recycling of streams and events (pool.hip; see fit_state.h)
-hipEvent_t event_take();
-void event_give(hipEvent_t e, int dev = -1);
-hipStream_t stream_take();
-void stream_give(hipStream_t s, int dev = -1);
-}  // namespace lsqamd_host
+#include "host.h"   // Carver, rup, the pools; through fit_state.h: FAIL, HIPCHK (they need ->err only), jit.h
 
 namespace lsqamd {
 
@@ -444,23 +437,18 @@ __global__ __launch_bounds__(256) void b_symmetrize_kernel(double *A, int64_t a_
 // ===============================================================================================
 using namespace lsqamd;
 
-namespace {
-constexpr int64_t ALIGNB = 256;
-inline int64_t rupb(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+using lsqamd_host::Carver;
+using lsqamd_host::rup;
 
-struct CarverB {
-  char *base;
-  size_t off = 0;
-  bool dry;
-  CarverB(void *b, bool d) : base((char *)b), dry(d) {}
-  template <typename T>
-  T *take(int64_t count) {
-    const size_t bytes = (size_t)rupb((count < 1 ? 1 : count) * (int64_t)sizeof(T), ALIGNB);
-    T *p = dry ? nullptr : reinterpret_cast<T *>(base + off);
-    off += bytes;
-    return p;
+using EventPairs = std::vector<std::pair<hipEvent_t, hipEvent_t>>;
+namespace {
+void give_events(EventPairs &v, int dev) {   // back to the pool, filed under the device they were taken on
+  for (auto &pr : v) {
+    lsqamd_host::event_give(pr.first, dev);
+    lsqamd_host::event_give(pr.second, dev);
   }
-};
+  v.clear();
+}
 }  // namespace
 
 struct lsqamdb_fits {
@@ -472,6 +460,9 @@ struct lsqamdb_fits {
   std::string err;
   int64_t N = 0, P = 0, ld = 0, ldm = 0, ncols_aug = 0, npk = 0, T = 0, nblk = 0;
   int32_t splits = 1, nparts = 256, nrparts = 64;
+  // derived sizes (carve_b): packed tiles per fit; per-fit strides of red = [packed A | g | chi2], of M / Wl / cov, of chol_work
+  int64_t ntile = 0, red_stride = 0, m_stride = 0, w_stride = 0;
+  double *gvec() const { return red + npk; }   // fit 0's [g | chi2] inside red
   // shared inputs
   double *x = nullptr, *ymean = nullptr, *wdiag = nullptr;
   int64_t ymean_stride = 0;  // 0 shared, N per-fit
@@ -503,30 +494,14 @@ struct lsqamdb_fits {
   // phase timers (lsqamdb_timing_enable): HIP events around the J^T J launch and the batched factorisation of every round;
   // rounds then run eagerly (events are not recorded into a captured graph)
   bool timing = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> tm_syrk, tm_chol;
+  EventPairs tm_syrk, tm_chol;
   ~lsqamdb_fits() {
-    for (auto *v : {&tm_syrk, &tm_chol})
-      for (auto &pr : *v) {
-        lsqamd_host::event_give(pr.first, dev);
-        lsqamd_host::event_give(pr.second, dev);
-      }
+    give_events(tm_syrk, dev);
+    give_events(tm_chol, dev);
   }
 };
 
 namespace {
-
-#define BFAIL(f, code, ...)                \
-  do {                                     \
-    char _b[512];                          \
-    snprintf(_b, sizeof(_b), __VA_ARGS__); \
-    (f)->err = _b;                         \
-    return (code);                         \
-  } while (0)
-#define BHIP(f, expr)                                                                      \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess) BFAIL(f, LSQAMD_EHIP, "%s: %s", #expr, hipGetErrorString(_e));  \
-  } while (0)
 
 // Synchronous copies go through the engine's OWN (non-blocking) stream, never the legacy default stream: a legacy-stream
 // operation synchronises with every blocking stream of the process and -- on this runtime -- fails with
@@ -550,14 +525,16 @@ size_t carve_b(lsqamdb_fits *f, void *ws, bool dry) {
   const lsqamd_config &c = f->cfg;
   const int64_t N = c.n_data, P = c.n_param, B = f->B;
   f->N = N; f->P = P;
-  f->ld = rupb(P + 1, 16);
-  f->ldm = (P % 128 == 0) ? P + 128 : rupb(P + 1, 16);
+  f->ld = rup(P + 1, 16);
+  f->ldm = (P % 128 == 0) ? P + 128 : rup(P + 1, 16);
   f->ncols_aug = (P % 128 == 0) ? P + 128 : P + 1;
   f->npk = packed_doubles(P);
   f->T = (P + 127) / 128;
   f->nblk = f->T;
+  f->ntile = f->T * (f->T + 1) / 2; f->red_stride = f->npk + P + 1;
+  f->m_stride = P * f->ldm; f->w_stride = f->nblk * 128 * 128;
   {  // split-K: enough workgroups over the whole batch
-    const int64_t tiles = f->T * (f->T + 1) / 2 * B;
+    const int64_t tiles = f->ntile * B;
     int64_t s = (4096 + tiles - 1) / tiles;
     const int64_t maxs = N / 1024 > 1 ? N / 1024 : 1;
     if (s > maxs) s = maxs;
@@ -569,9 +546,8 @@ size_t carve_b(lsqamdb_fits *f, void *ws, bool dry) {
     }
     f->splits = (int32_t)s;
   }
-  f->nparts = 64;
-  f->nrparts = 32;
-  CarverB cv(ws, dry);
+  f->nparts = 64; f->nrparts = 32;
+  Carver cv(ws, 0, dry);
   f->x = cv.take<double>(N * (c.n_x > 0 ? c.n_x : 1));
   f->ymean = cv.take<double>(B * N);
   f->wdiag = cv.take<double>(N);
@@ -593,15 +569,15 @@ size_t carve_b(lsqamdb_fits *f, void *ws, bool dry) {
   f->diag = cv.take<double>(B * P);
   f->r = cv.take<double>(B * N);
   f->J = cv.take<double>(B * N * f->ld);
-  f->slabs = cv.take<double>(B * f->splits * P * f->ldm);
-  f->red = cv.take<double>(B * (f->npk + P + 1));
-  f->M = cv.take<double>(B * P * f->ldm);
-  f->chol_work = cv.take<double>(B * f->nblk * 128 * 128);
+  f->slabs = cv.take<double>(B * f->splits * f->m_stride);
+  f->red = cv.take<double>(B * f->red_stride);
+  f->M = cv.take<double>(B * f->m_stride);
+  f->chol_work = cv.take<double>(B * f->w_stride);
   f->yv = cv.take<double>(B * 2 * P);
   f->partial = cv.take<double>(B * f->nparts * (P + 1));
   f->spart = cv.take<double>(B * f->nrparts);
-  f->Wl = cv.take<double>(B * P * f->ldm);
-  f->cov = cv.take<double>(B * P * f->ldm);
+  f->Wl = cv.take<double>(B * f->m_stride);
+  f->cov = cv.take<double>(B * f->m_stride);
   f->logdet = cv.take<double>(B);
   f->s.mu = cv.take<double>(B); f->s.chi2 = cv.take<double>(B); f->s.chi2t = cv.take<double>(B);
   f->s.vg = cv.take<double>(B); f->s.dv2 = cv.take<double>(B);
@@ -647,14 +623,30 @@ ModelArgs model_args_b(const lsqamdb_fits *f, const double *p) {
   return m;
 }
 
-// Jacobian, J^T J (packed), J^T f, chi2 for every fit flagged in `mask` at its current x (inside a
-// round: the fits whose trial was accepted -- a rejected trial leaves x, J and the sums as they are)
-int normal_all(lsqamdb_fits *f, const int32_t *mask) {
-  const int64_t P = f->P, N = f->N, B = f->B;
+struct Bracket {   // HIP-event bracket around one launch while the handle's timers are on (lsqamd_host::Scope's counterpart)
+  lsqamdb_fits *f;
+  EventPairs &into;
+  hipEvent_t a = nullptr, b = nullptr;
+  Bracket(lsqamdb_fits *fits, EventPairs &list, bool on = true) : f(fits), into(list) {
+    if (!on || !f->timing) return;
+    a = lsqamd_host::event_take();
+    b = lsqamd_host::event_take();
+    (void)hipEventRecord(a, f->st);
+  }
+  ~Bracket() {   // filed whether or not the launch went through: the list owns the pair from here on
+    if (!a) return;
+    (void)hipEventRecord(b, f->st);
+    into.emplace_back(a, b);
+  }
+};
+
+// the whitened Jacobian (its last column: the residual) of every fit flagged in `mask` at its current x
+int jacobian_all(lsqamdb_fits *f, const int32_t *mask) {
+  const int64_t P = f->P, N = f->N;
   ModelArgs m = model_args_b(f, f->px);
   m.batch_active = mask;
   m.out_stride = N * f->ld;
-  BHIP(f, launch_jacobian_ex(f->st, m, f->J, f->cfg.n_blocks > 0 ? f->Jraw : nullptr, f->ld));
+  HIPCHK(f, launch_jacobian_ex(f->st, m, f->J, f->cfg.n_blocks > 0 ? f->Jraw : nullptr, f->ld));
   // block rows: J_b <- W_b . Jraw_b for every fit (W shared: X stride 0, batch = fits)
   for (size_t k = 0; k < f->h_size.size(); ++k) {
     const int64_t Bk = f->h_size[k];
@@ -664,17 +656,21 @@ int normal_all(lsqamdb_fits *f, const int32_t *mask) {
     w.C = f->J + f->h_row0[k] * f->ld; w.ldc = f->ld; w.sc = N * f->ld;
     w.M = Bk; w.N = P + 1; w.K = Bk;
     w.x_upper_tri = f->h_tri[k];
-    w.batch = (int32_t)B; w.batch_active = mask;
-    BHIP(f, launch_gemm_tn(f->st, w));
+    w.batch = (int32_t)f->B; w.batch_active = mask;
+    HIPCHK(f, launch_gemm_tn(f->st, w));
   }
+  return 0;
+}
+
+// J^T J -> packed tiles, J^T f and |f|^2 -> [g | chi2], from the Jacobian jacobian_all left
+int product_all(lsqamdb_fits *f, const int32_t *mask) {
+  const int64_t P = f->P, N = f->N;
+  const unsigned B = (unsigned)f->B;
   GemmTN g;
-  g.X = f->J; g.Y = f->J; g.ldx = g.ldy = f->ld;
-  g.sx = g.sy = N * f->ld;
-  g.C = f->slabs; g.ldc = f->ldm; g.sc = (int64_t)f->splits * P * f->ldm;
+  g.X = f->J; g.Y = f->J; g.ldx = g.ldy = f->ld; g.sx = g.sy = N * f->ld;
+  g.C = f->slabs; g.ldc = f->ldm; g.sc = (int64_t)f->splits * f->m_stride;
   g.M = P; g.N = P; g.K = N;
-  g.upper_only = 1;
-  g.splits = f->splits;
-  g.split_stride = P * f->ldm;
+  g.upper_only = 1; g.splits = f->splits; g.split_stride = f->m_stride;
   g.work_map = f->syrk_map; g.n_work = f->syrk_nwork;
   g.batch = (int32_t)B; g.batch_active = mask;
   // J^T f and chi2 from the diagonal tiles of the same launch when it is the kernel that can (P a multiple of 128):
@@ -682,46 +678,51 @@ int normal_all(lsqamdb_fits *f, const int32_t *mask) {
   g.colsum_out = f->partial; g.colsum_ld = P + 1; g.colsum_rcol = P;
   const bool syrk_colsum = gemm_tn_fuses_colsum(g);
   if (!syrk_colsum) g.colsum_out = nullptr;
-  if (f->timing) {
-    hipEvent_t a = lsqamd_host::event_take(), b = lsqamd_host::event_take();
-    (void)hipEventRecord(a, f->st);
-    BHIP(f, launch_gemm_tn(f->st, g));
-    (void)hipEventRecord(b, f->st);
-    f->tm_syrk.emplace_back(a, b);
-  } else {
-    BHIP(f, launch_gemm_tn(f->st, g));
+  {
+    Bracket tb(f, f->tm_syrk);
+    HIPCHK(f, launch_gemm_tn(f->st, g));
   }
-  const int64_t red_stride = f->npk + P + 1;
-  hipLaunchKernelGGL(b_finalize_pack_kernel, dim3((unsigned)(f->T * (f->T + 1) / 2), 16, (unsigned)B),
-                     dim3(256), 0, f->st, f->slabs, f->splits, P * f->ldm, (int64_t)f->splits * P * f->ldm, P,
-                     f->ldm, f->T, f->red, red_stride, mask);
-  if (syrk_colsum) {
-    hipLaunchKernelGGL(b_colsum_stage2, dim3((unsigned)((P + 1 + 255) / 256), (unsigned)B), dim3(256), 0, f->st,
-                       f->partial, (int64_t)f->splits, P + 1, (int64_t)f->splits * (P + 1), f->red + f->npk, red_stride,
-                       mask);
-  } else {
-    int64_t nchunks = f->nparts;
+  hipLaunchKernelGGL(b_finalize_pack_kernel, dim3((unsigned)f->ntile, 16, B), dim3(256), 0, f->st, f->slabs, f->splits,
+                     f->m_stride, (int64_t)f->splits * f->m_stride, P, f->ldm, f->T, f->red, f->red_stride, mask);
+  int64_t nchunks = f->splits, part_stride = (int64_t)f->splits * (P + 1);
+  if (!syrk_colsum) {
+    nchunks = f->nparts;
     if (nchunks > N) nchunks = N;
     const int64_t rpc = (N + nchunks - 1) / nchunks;
     nchunks = (N + rpc - 1) / rpc;
-    hipLaunchKernelGGL(b_colsum_stage1, dim3((unsigned)((P + 1 + 511) / 512), (unsigned)nchunks, (unsigned)B),
-                       dim3(256), 0, f->st, f->J, N, f->ld, P + 1, P, rpc, N * f->ld, f->partial,
-                       (int64_t)f->nparts * (P + 1), mask);
-    hipLaunchKernelGGL(b_colsum_stage2, dim3((unsigned)((P + 1 + 255) / 256), (unsigned)B), dim3(256), 0, f->st,
-                       f->partial, nchunks, P + 1, (int64_t)f->nparts * (P + 1), f->red + f->npk, red_stride,
-                       mask);
+    part_stride = (int64_t)f->nparts * (P + 1);
+    hipLaunchKernelGGL(b_colsum_stage1, dim3((unsigned)((P + 1 + 511) / 512), (unsigned)nchunks, B), dim3(256), 0, f->st, f->J,
+                       N, f->ld, P + 1, P, rpc, N * f->ld, f->partial, part_stride, mask);
   }
+  hipLaunchKernelGGL(b_colsum_stage2, dim3((unsigned)((P + 1 + 255) / 256), B), dim3(256), 0, f->st, f->partial, nchunks, P + 1,
+                     part_stride, f->gvec(), f->red_stride, mask);
+  return 0;
+}
+
+// Lambda (x - pbar) of every fit flagged in `mask` (dense shared prior) -> f->ptvec
+void prior_vec_dense(lsqamdb_fits *f, const double *x, const int32_t *mask) {
+  hipLaunchKernelGGL(b_prior_vec_dense_kernel, dim3((unsigned)((f->P + 3) / 4), (unsigned)f->B), dim3(256), 0, f->st, f->P,
+                     f->pprec, f->pmean, x, f->ptvec, mask);
+}
+
+// Jacobian, J^T J (packed), J^T f, chi2, then the prior's share of all three, for every fit flagged in `mask` at its current x
+// (inside a round: the fits whose trial was accepted -- a rejected trial leaves x, J and the sums as they are)
+int normal_all(lsqamdb_fits *f, const int32_t *mask) {
+  int rc = jacobian_all(f, mask);
+  if (rc || (rc = product_all(f, mask))) return rc;
+  const int64_t P = f->P;
+  const unsigned B = (unsigned)f->B;
   if (f->cfg.has_prior && f->cfg.prior_dense) {
-    hipLaunchKernelGGL(b_prior_matrix_dense_kernel, dim3((unsigned)(f->T * (f->T + 1) / 2), 16, (unsigned)B),
-                       dim3(256), 0, f->st, f->red, red_stride, P, f->T, f->pprec, mask);
-    hipLaunchKernelGGL(b_prior_vec_dense_kernel, dim3((unsigned)((P + 3) / 4), (unsigned)B), dim3(256), 0, f->st,
-                       P, f->pprec, f->pmean, f->px, f->ptvec, mask);
-    hipLaunchKernelGGL(b_prior_apply_kernel, dim3((unsigned)B), dim3(256), 0, f->st, P, f->pmean, f->px, f->ptvec,
-                       f->red + f->npk, red_stride, mask);
-  } else if (f->cfg.has_prior)
-    hipLaunchKernelGGL(b_prior_kernel, dim3((unsigned)B), dim3(256), 0, f->st, P, f->T, f->pprec, f->pmean,
-                       f->px, f->red, red_stride, f->red + f->npk, red_stride, mask);
-  BHIP(f, hipGetLastError());
+    hipLaunchKernelGGL(b_prior_matrix_dense_kernel, dim3((unsigned)f->ntile, 16, B), dim3(256), 0, f->st, f->red,
+                       f->red_stride, P, f->T, f->pprec, mask);
+    prior_vec_dense(f, f->px, mask);
+    hipLaunchKernelGGL(b_prior_apply_kernel, dim3(B), dim3(256), 0, f->st, P, f->pmean, f->px, f->ptvec, f->gvec(),
+                       f->red_stride, mask);
+  } else if (f->cfg.has_prior) {
+    hipLaunchKernelGGL(b_prior_kernel, dim3(B), dim3(256), 0, f->st, P, f->T, f->pprec, f->pmean, f->px, f->red,
+                       f->red_stride, f->gvec(), f->red_stride, mask);
+  }
+  HIPCHK(f, hipGetLastError());
   return 0;
 }
 
@@ -730,82 +731,80 @@ int trial_chi2_all(lsqamdb_fits *f) {
   const int64_t P = f->P, N = f->N, B = f->B;
   ModelArgs m = model_args_b(f, f->pxt);
   m.out_stride = N;
-  BHIP(f, launch_residual_ex(f->st, m, f->r, f->cfg.n_blocks > 0 ? f->r_raw : nullptr));
+  HIPCHK(f, launch_residual_ex(f->st, m, f->r, f->cfg.n_blocks > 0 ? f->r_raw : nullptr));
   if (f->cfg.n_blocks > 0)
-    BHIP(f, launch_block_whiten_vec(f->st, f->wt, f->blk_row0, f->blk_size, f->blk_woff, f->cfg.n_blocks,
-                                    f->cfg.max_block, f->r_raw, f->r, (int32_t)B, N, f->s.active));
+    HIPCHK(f, launch_block_whiten_vec(f->st, f->wt, f->blk_row0, f->blk_size, f->blk_woff, f->cfg.n_blocks,
+                                      f->cfg.max_block, f->r_raw, f->r, (int32_t)B, N, f->s.active));
   hipLaunchKernelGGL(b_sumsq_stage1, dim3((unsigned)f->nrparts, (unsigned)B), dim3(256), 0, f->st, f->r, N, N,
                      f->spart, f->nrparts, f->s.active);
   const bool dense_prior = f->cfg.has_prior && f->cfg.prior_dense;
-  if (dense_prior)
-    hipLaunchKernelGGL(b_prior_vec_dense_kernel, dim3((unsigned)((P + 3) / 4), (unsigned)B), dim3(256), 0, f->st,
-                       P, f->pprec, f->pmean, f->pxt, f->ptvec, f->s.active);
+  if (dense_prior) prior_vec_dense(f, f->pxt, f->s.active);
   hipLaunchKernelGGL(b_sumsq_stage2, dim3((unsigned)B), dim3(256), 0, f->st, f->spart, f->nrparts, P, f->pprec,
                      f->pmean, f->pxt, f->cfg.has_prior, dense_prior ? f->ptvec : nullptr, f->s);
   return 0;
 }
 
+// (A_b + mu_b D_b^2 | g_b) -- with_damping = 0: (A_b | g_b) -- built, factored and back-substituted for every fit flagged in
+// `mask`: v_b lands in f->yv[b][P..2P), a failed pivot in s.cholinfo[b].  timed: the factorisation counts for the cholesky timer
+int factor_and_solve(lsqamdb_fits *f, const int32_t *mask, int with_damping, bool timed) {
+  const int64_t P = f->P;
+  const int32_t B = f->B;
+  hipLaunchKernelGGL(b_build_damped_kernel, dim3((unsigned)f->ntile, 16, (unsigned)B), dim3(256), 0, f->st, f->red,
+                     f->red_stride, P, f->T, f->ldm, f->s.mu, f->diag, f->gvec(), f->red_stride, f->M, f->m_stride, mask,
+                     with_damping);
+  {
+    Bracket tb(f, f->tm_chol, timed);
+    HIPCHK(f, potrf_upper_batched(f->st, f->M, P, f->ldm, f->ncols_aug, f->chol_work, f->s.cholinfo, B, f->m_stride,
+                                  f->w_stride, mask));
+  }
+  hipLaunchKernelGGL(b_extract_y_kernel, dim3((unsigned)((P + 255) / 256), (unsigned)B), dim3(256), 0, f->st, f->M,
+                     f->m_stride, f->ldm, P, f->yv, 2 * P, mask);
+  HIPCHK(f, backsolve_upper_batched(f->st, f->M, P, f->ldm, f->chol_work, f->yv, B, f->m_stride, f->w_stride, 2 * P, mask));
+  return 0;
+}
+
+// the tail of a round of either kind: the accepted fits move, get new normal equations, then the scaling update, niter and
+// the convergence tests of every active fit
+int commit_normal_post(lsqamdb_fits *f) {
+  const int64_t P = f->P;
+  const unsigned B = (unsigned)f->B;
+  hipLaunchKernelGGL(b_commit_kernel, dim3((unsigned)((P + 255) / 256), B), dim3(256), 0, f->st, P, f->px, f->pxt, f->s);
+  const int rc = normal_all(f, f->s.moved);
+  if (rc) return rc;
+  hipLaunchKernelGGL(b_post_kernel, dim3(B), dim3(256), 0, f->st, P, f->T, f->red, f->red_stride, f->gvec(), f->red_stride,
+                     f->diag, f->px, f->dx, f->opt.scaler, f->opt.xtol, f->opt.gtol, f->opt.maxit, f->s);
+  return 0;
+}
+
 int round_all(lsqamdb_fits *f) {
   const int64_t P = f->P, B = f->B;
-  const int64_t red_stride = f->npk + P + 1, m_stride = P * f->ldm, w_stride = f->nblk * 128 * 128;
-  const unsigned ntile = (unsigned)(f->T * (f->T + 1) / 2);
-  hipLaunchKernelGGL(b_build_damped_kernel, dim3(ntile, 16, (unsigned)B), dim3(256), 0, f->st, f->red,
-                     red_stride, P, f->T, f->ldm, f->s.mu, f->diag, f->red + f->npk, red_stride, f->M, m_stride,
-                     f->s.active, 1);
-  if (f->timing) {
-    hipEvent_t a = lsqamd_host::event_take(), b = lsqamd_host::event_take();
-    (void)hipEventRecord(a, f->st);
-    BHIP(f, potrf_upper_batched(f->st, f->M, P, f->ldm, f->ncols_aug, f->chol_work, f->s.cholinfo, (int32_t)B,
-                                m_stride, w_stride, f->s.active));
-    (void)hipEventRecord(b, f->st);
-    f->tm_chol.emplace_back(a, b);
-  } else {
-    BHIP(f, potrf_upper_batched(f->st, f->M, P, f->ldm, f->ncols_aug, f->chol_work, f->s.cholinfo, (int32_t)B,
-                                m_stride, w_stride, f->s.active));
-  }
-  hipLaunchKernelGGL(b_extract_y_kernel, dim3((unsigned)((P + 255) / 256), (unsigned)B), dim3(256), 0, f->st,
-                     f->M, m_stride, f->ldm, P, f->yv, 2 * P, f->s.active);
-  BHIP(f, backsolve_upper_batched(f->st, f->M, P, f->ldm, f->chol_work, f->yv, (int32_t)B, m_stride, w_stride,
-                                  2 * P, f->s.active));
-  hipLaunchKernelGGL(b_trial_kernel, dim3((unsigned)B), dim3(256), 0, f->st, P, f->yv, 2 * P, f->px,
-                     f->red + f->npk, red_stride, f->diag, f->dx, f->pxt, f->s);
-  int rc = trial_chi2_all(f);
+  int rc = factor_and_solve(f, f->s.active, 1, true);
   if (rc) return rc;
+  hipLaunchKernelGGL(b_trial_kernel, dim3((unsigned)B), dim3(256), 0, f->st, P, f->yv, 2 * P, f->px, f->gvec(),
+                     f->red_stride, f->diag, f->dx, f->pxt, f->s);
+  if ((rc = trial_chi2_all(f))) return rc;
   hipLaunchKernelGGL(b_decide_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, f->st, (int)B,
                      f->opt.factor_up, f->opt.factor_down, f->s);
-  hipLaunchKernelGGL(b_commit_kernel, dim3((unsigned)((P + 255) / 256), (unsigned)B), dim3(256), 0, f->st, P,
-                     f->px, f->pxt, f->s);
-  rc = normal_all(f, f->s.moved);
-  if (rc) return rc;
-  hipLaunchKernelGGL(b_post_kernel, dim3((unsigned)B), dim3(256), 0, f->st, P, f->T, f->red, red_stride,
-                     f->red + f->npk, red_stride, f->diag, f->px, f->dx, f->opt.scaler, f->opt.xtol, f->opt.gtol,
-                     f->opt.maxit, f->s);
+  if ((rc = commit_normal_post(f))) return rc;
   hipLaunchKernelGGL(b_count_kernel, dim3(1), dim3(256), 0, f->st, (int)B, f->s);
-  BHIP(f, hipGetLastError());
+  HIPCHK(f, hipGetLastError());
   return 0;
 }
 
 // ---- the dogleg family (opt.trs = DOGLEG / DDOGLEG / SUBSPACE2D; kernels in batch_trs.hip) ------------------------------
 // The two legs of every fit flagged in `mask` at its current (A, g, D): w = D^-2 g, ONE symmetric product for w^T A w, the
 // Gauss-Newton point from the undamped normal equations (the same build / factorisation / back substitution as an LM trial,
-// with mu = 0), then the scalars the step kernel works from.
+// with mu = 0; not counted by the cholesky timer), then the scalars the step kernel works from.
 int legs_all(lsqamdb_fits *f, const int32_t *mask) {
-  const int64_t P = f->P, B = f->B;
-  const int64_t red_stride = f->npk + P + 1, m_stride = P * f->ldm, w_stride = f->nblk * 128 * 128;
-  const unsigned ntile = (unsigned)(f->T * (f->T + 1) / 2);
-  const double *gvec = f->red + f->npk;
-  BHIP(f, launch_trs_grad(f->st, P, (int32_t)B, gvec, red_stride, f->diag, f->t, mask));
-  BHIP(f, launch_symv_packed(f->st, f->red, red_stride, P, (int32_t)B, f->t.w, P, f->t.part, f->t.aw, P, f->t.rec + TR_WAW,
-                             TR_COUNT, mask));
-  hipLaunchKernelGGL(b_build_damped_kernel, dim3(ntile, 16, (unsigned)B), dim3(256), 0, f->st, f->red, red_stride, P, f->T,
-                     f->ldm, f->s.mu, f->diag, gvec, red_stride, f->M, m_stride, mask, 0);
-  BHIP(f, potrf_upper_batched(f->st, f->M, P, f->ldm, f->ncols_aug, f->chol_work, f->s.cholinfo, (int32_t)B, m_stride,
-                              w_stride, mask));
-  hipLaunchKernelGGL(b_extract_y_kernel, dim3((unsigned)((P + 255) / 256), (unsigned)B), dim3(256), 0, f->st, f->M, m_stride,
-                     f->ldm, P, f->yv, 2 * P, mask);
-  BHIP(f, backsolve_upper_batched(f->st, f->M, P, f->ldm, f->chol_work, f->yv, (int32_t)B, m_stride, w_stride, 2 * P, mask));
-  BHIP(f, launch_trs_legs(f->st, P, (int32_t)B, f->opt.trs, gvec, red_stride, f->diag, f->yv + P, 2 * P, f->s.cholinfo, f->t,
-                          mask));
+  const int64_t P = f->P;
+  const int32_t B = f->B;
+  HIPCHK(f, launch_trs_grad(f->st, P, B, f->gvec(), f->red_stride, f->diag, f->t, mask));
+  HIPCHK(f, launch_symv_packed(f->st, f->red, f->red_stride, P, B, f->t.w, P, f->t.part, f->t.aw, P, f->t.rec + TR_WAW,
+                               TR_COUNT, mask));
+  const int rc = factor_and_solve(f, mask, 0, false);
+  if (rc) return rc;
+  HIPCHK(f, launch_trs_legs(f->st, P, B, f->opt.trs, f->gvec(), f->red_stride, f->diag, f->yv + P, 2 * P, f->s.cholinfo, f->t,
+                            mask));
   return 0;
 }
 
@@ -813,28 +812,165 @@ int legs_all(lsqamdb_fits *f, const int32_t *mask) {
 // the accepted fits move, get new normal equations, the scaling update and the convergence tests (b_post_kernel, as in LM)
 // -> new legs for the fits that moved and go on.  A fit that rejected keeps its legs: no product, no factorisation.
 int round_trs(lsqamdb_fits *f) {
-  const int64_t P = f->P, B = f->B;
-  const int64_t red_stride = f->npk + P + 1;
-  BHIP(f, launch_trs_step(f->st, P, (int32_t)B, f->opt.trs, f->px, f->pxt, f->dx, f->t, f->s.active));
+  const int32_t B = f->B;
+  HIPCHK(f, launch_trs_step(f->st, f->P, B, f->opt.trs, f->px, f->pxt, f->dx, f->t, f->s.active));
   int rc = trial_chi2_all(f);
   if (rc) return rc;
-  BHIP(f, launch_trs_decide(f->st, (int32_t)B, f->opt.factor_up, f->opt.factor_down, f->s, f->t));
-  hipLaunchKernelGGL(b_commit_kernel, dim3((unsigned)((P + 255) / 256), (unsigned)B), dim3(256), 0, f->st, P,
-                     f->px, f->pxt, f->s);
-  rc = normal_all(f, f->s.moved);
-  if (rc) return rc;
-  hipLaunchKernelGGL(b_post_kernel, dim3((unsigned)B), dim3(256), 0, f->st, P, f->T, f->red, red_stride,
-                     f->red + f->npk, red_stride, f->diag, f->px, f->dx, f->opt.scaler, f->opt.xtol, f->opt.gtol,
-                     f->opt.maxit, f->s);
-  BHIP(f, launch_trs_mask(f->st, (int32_t)B, f->s, f->t));
-  rc = legs_all(f, f->t.lmask);
-  if (rc) return rc;
+  HIPCHK(f, launch_trs_decide(f->st, B, f->opt.factor_up, f->opt.factor_down, f->s, f->t));
+  if ((rc = commit_normal_post(f))) return rc;
+  HIPCHK(f, launch_trs_mask(f->st, B, f->s, f->t));
+  if ((rc = legs_all(f, f->t.lmask))) return rc;
   hipLaunchKernelGGL(b_count_kernel, dim3(1), dim3(256), 0, f->st, (int)B, f->s);
-  BHIP(f, hipGetLastError());
+  HIPCHK(f, hipGetLastError());
   return 0;
 }
 
 int round_any(lsqamdb_fits *f) { return f->opt.trs == LSQAMD_TRS_LM ? round_all(f) : round_trs(f); }
+
+// ---- the stages of lsqamdb_run -------------------------------------------------------------------------------------
+int inputs_ready(lsqamdb_fits *f) {
+  if (!f->have_data || (f->cfg.has_prior && !f->have_prior) || (f->cfg.n_blocks > 0 && !f->have_blocks) ||
+      (f->cfg.model != LSQAMD_MODEL_IDENTITY && !f->have_x) || (f->cfg.model == LSQAMD_MODEL_TAPE && !f->have_tape))
+    FAIL(f, LSQAMD_EINVAL, "run: inputs missing");
+  return 0;
+}
+
+struct RunSpan {   // the two events a run's device time is read from: every return path gives them back
+  lsqamdb_fits *f;
+  hipEvent_t e0 = lsqamd_host::event_take(), e1 = lsqamd_host::event_take();
+  ~RunSpan() { lsqamd_host::event_give(e0, f->dev); lsqamd_host::event_give(e1, f->dev); }
+};
+
+// every fit active (the host's vector is pageable: the stream is waited for before it goes)
+int activate_all(lsqamdb_fits *f) {
+  std::vector<int32_t> ones((size_t)f->B, 1);
+  HIPCHK(f, hipMemcpyAsync(f->s.active, ones.data(), sizeof(int32_t) * f->B, hipMemcpyHostToDevice, f->st));
+  HIPCHK(f, hipStreamSynchronize(f->st));
+  return 0;
+}
+
+// the state either route starts from: x = p0, every fit active
+int start_at(lsqamdb_fits *f, const double *p0) {
+  HIPCHK(f, hipMemcpyAsync(f->px, p0, sizeof(double) * f->B * f->P, hipMemcpyHostToDevice, f->st));
+  return activate_all(f);
+}
+
+// Small fits (a compiled formula, <= 12 parameters, <= 4096 uncorrelated rows or <= 256 with covariance blocks): every
+// fit of the batch is ONE workgroup of ONE launch (jit.hip lsqamd_jit_lmb -- the loop of the single-fit kernel, lm_driver.hip
+// run_one_launch) instead of ~20 lockstep launches per round.  -> 1: done (rounds, one_launch, have_cov_from_run set); 0: not
+// this batch's route, or the kernel met an irregular fit and the lockstep engine runs the whole batch from the start (p0
+// again, every fit active); < 0: error.  LSQAMD_ONE_LAUNCH_FIT=0 disables (read per call).
+int try_one_launch(lsqamdb_fits *f, const double *p0) {
+  f->one_launch = false;
+  const int64_t P = f->P, B = f->B;
+  const char *e = getenv("LSQAMD_ONE_LAUNCH_FIT");
+  if (e && e[0] == '0') return 0;
+  const lsqamd_jit::Kernel *k = static_cast<const lsqamd_jit::Kernel *>(f->jit);
+  if (!lsqamd_jit::has_batch_fit_kernel(k) || P > lsqamd_jit::FIT_MAX_P || f->N < 1 ||
+      f->N > lsqamd_jit::fit_row_limit(k, f->cfg.n_blocks != 0) || f->cfg.n_blocks > 64) return 0;
+  if (f->opt.maxit < 1 || f->opt.maxit > 20000 || f->opt.trs != LSQAMD_TRS_LM) return 0;
+  lsqamd_jit::FitArgs a;
+  a.x = f->x; a.ymean = f->ymean; a.wdiag = f->wdiag; a.n_data = f->N;
+  a.in_block = f->in_block; a.wt = f->wt;
+  a.blk_row0 = reinterpret_cast<const long long *>(f->blk_row0); a.blk_size = reinterpret_cast<const long long *>(f->blk_size);
+  a.blk_woff = reinterpret_cast<const long long *>(f->blk_woff); a.n_blocks = f->cfg.n_blocks;
+  a.p0 = f->px; a.p = f->px; a.p_trial = f->pxt; a.dscale = f->diag; a.apk = f->red; a.gvec = f->gvec();
+  a.v_out = f->dx; a.coln2 = nullptr; a.st = nullptr;
+  a.prior_prec = f->cfg.has_prior ? f->pprec : nullptr; a.prior_mean = f->cfg.has_prior ? f->pmean : nullptr;
+  a.prior_dense = f->cfg.prior_dense; a.scaler = f->opt.scaler; a.maxit = f->opt.maxit; a.watch = 0;
+  a.xtol = f->opt.xtol; a.gtol = f->opt.gtol; a.factor_up = f->opt.factor_up; a.factor_down = f->opt.factor_down;
+  a.hostptr_bits = 0.0; a.cov = f->cov; a.ldc = f->ldm; a.want_cov = 1; a.pad_ = 0;
+  a.host = f->chol_work;                       // (free until a covariance is asked for: 16384 doubles per fit)
+  a.pub = nullptr; a.seq = 0;                  // (the batch's results are copied after a stream synchronisation)
+  lsqamd_jit::FitBatch bt;
+  bt.ymean_stride = f->ymean_stride; bt.prec_stride = f->cfg.prior_dense ? 0 : P; bt.tile_stride = f->red_stride;
+  bt.cov_stride = f->m_stride; bt.scratch_stride = f->w_stride;
+  bt.logdet = f->logdet; bt.mu = f->s.mu; bt.chi2 = f->s.chi2;
+  bt.nit = f->s.nit; bt.info = f->s.info; bt.status = f->s.status; bt.nfev = f->s.nfev; bt.njev = f->s.njev;
+  bt.active = f->s.active; bt.reason = f->s.bad;
+  HIPCHK(f, lsqamd_jit::launch_fit_batch(k, f->st, a, bt, (int)B));
+  std::vector<int32_t> reason((size_t)B, 0);
+  HIPCHK(f, hipMemcpyAsync(reason.data(), f->s.bad, sizeof(int32_t) * B, hipMemcpyDeviceToHost, f->st));
+  HIPCHK(f, hipStreamSynchronize(f->st));
+  bool all_done = true, all_cov = true;
+  for (int32_t r : reason) {
+    all_done = all_done && (r == 1 || r == 3);
+    all_cov = all_cov && r == 1;
+  }
+  if (!all_done) return start_at(f, p0);
+  f->one_launch = true;
+  f->rounds = 1;
+  f->graph_used = 0;
+  f->have_cov_from_run = all_cov;
+  return 1;
+}
+
+// the lockstep engine's state at p0: normal equations, D, mu (b_init_kernel), for the dogleg family its trust radius and the
+// legs; no graph from an earlier run (kernel arguments -- tolerances, maxit, factors -- are baked into graph nodes)
+int start_lockstep(lsqamdb_fits *f) {
+  int rc = normal_all(f, f->s.active);
+  if (rc) return rc;
+  hipLaunchKernelGGL(b_init_kernel, dim3((unsigned)f->B), dim3(256), 0, f->st, f->P, f->T, f->red, f->red_stride, f->gvec(),
+                     f->red_stride, f->diag, f->opt.scaler, f->s);
+  if (f->opt.trs != LSQAMD_TRS_LM) {
+    HIPCHK(f, launch_trs_init(f->st, f->P, f->B, f->diag, f->px, f->t));
+    if ((rc = legs_all(f, f->s.active))) return rc;
+  }
+  f->rounds = 0;
+  f->graph_used = 0;
+  if (f->gexec) { (void)hipGraphExecDestroy(f->gexec); f->gexec = nullptr; }
+  if (f->graph) { (void)hipGraphDestroy(f->graph); f->graph = nullptr; }
+  return 0;
+}
+
+// One attempt at capturing a round into f->gexec (nothing runs: the caller launches it).  f->gexec stays null when the capture
+// or the instantiation failed -- the caller goes on eagerly, on a stream that has been reset.  Non-zero: a launch of the round
+// failed although the capture itself came through.
+int capture_round(lsqamdb_fits *f) {
+  if (hipStreamBeginCapture(f->st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+    const int rc = round_any(f);
+    hipGraph_t gr = nullptr;
+    const hipError_t e = hipStreamEndCapture(f->st, &gr);
+    // a capture another thread's activity invalidated makes the captured launches fail too: that is a failed CAPTURE
+    // (nothing ran, nothing changed on the device), not a failed round -- the caller's round runs eagerly
+    if (rc && e == hipSuccess) return rc;
+    if (e == hipSuccess && gr && hipGraphInstantiate(&f->gexec, gr, nullptr, nullptr, 0) == hipSuccess) {
+      f->graph = gr;
+    } else {
+      if (gr) (void)hipGraphDestroy(gr);
+      f->gexec = nullptr;
+      capture_reset(f->st);      // (an invalidated capture leaves the stream unusable until it is reset: common.h)
+    }
+  }
+  (void)hipGetLastError();
+  return 0;
+}
+
+// the per-fit scalars lie one after the other in the workspace (carve_b: s.mu .. s.njev): ONE copy instead of seven
+int write_summaries(lsqamdb_fits *f, lsqamd_summary *summaries, float ms) {
+  const int64_t B = f->B;
+  const char *lo = reinterpret_cast<const char *>(f->s.mu), *hi = reinterpret_cast<const char *>(f->s.njev + B);
+  std::vector<char> span((size_t)(hi - lo));
+  HIPCHK(f, copy_sync(f, span.data(), lo, span.size(), hipMemcpyDeviceToHost));
+  auto at = [&](const auto *dev) {   // the host copy of a device array inside the span
+    return reinterpret_cast<decltype(dev)>(span.data() + (reinterpret_cast<const char *>(dev) - lo));
+  };
+  const double *mu = at(f->s.mu), *chi2 = at(f->s.chi2);
+  const int32_t *nit = at(f->s.nit), *info = at(f->s.info), *status = at(f->s.status), *nfev = at(f->s.nfev), *njev = at(f->s.njev);
+  for (int64_t b = 0; b < B; ++b) {
+    lsqamd_summary &s = summaries[b];
+    std::memset(&s, 0, sizeof(s));
+    s.status = status[b] == -2 ? LSQAMD_EMAXITER : status[b];
+    s.info = info[b];
+    s.stopping_criterion = (info[b] >= 0 && info[b] <= 3) ? info[b] : (info[b] == 27 ? 4 : 0);
+    s.nit = nit[b]; s.nfev = nfev[b]; s.njev = njev[b]; s.ntrial = nfev[b] - 1;
+    s.chi2 = chi2[b]; s.mu = mu[b];
+    s.logdet_jtj = NAN;
+    s.t_run_ms = ms;
+    s.t_setup_ms = (double)f->graph_used;  // rounds replayed from the captured graph
+  }
+  return 0;
+}
 
 }  // namespace
 
@@ -872,7 +1008,7 @@ int lsqamdb_create(const lsqamd_config *cfg, int32_t n_fits, void *dev_workspace
   std::vector<int32_t> wm(4 * (size_t)f->syrk_nwork);
   syrk_work_fill(f->P, f->splits, wm.data());
   if (hipMemcpyAsync(f->syrk_map, wm.data(), wm.size() * sizeof(int32_t), hipMemcpyHostToDevice, f->st) != hipSuccess ||
-      hipMemsetAsync(f->M, 0, sizeof(double) * (size_t)(f->B * f->P * f->ldm), f->st) != hipSuccess ||
+      hipMemsetAsync(f->M, 0, sizeof(double) * (size_t)(f->B * f->m_stride), f->st) != hipSuccess ||
       hipStreamSynchronize(f->st) != hipSuccess) {
     (void)hipStreamSynchronize(f->st);
     lsqamd_host::stream_give(f->st, f->dev);
@@ -898,8 +1034,8 @@ const char *lsqamdb_last_error(const lsqamdb_fits *f) { return f ? f->err.c_str(
 
 int lsqamdb_set_x(lsqamdb_fits *f, const double *x, int64_t n_rows, int32_t n_x) try {
   if (!f) return LSQAMD_EINVAL;
-  if (!x || n_rows != f->N || n_x != (f->cfg.n_x > 0 ? f->cfg.n_x : 1)) BFAIL(f, LSQAMD_EINVAL, "set_x: shape");
-  BHIP(f, copy_sync(f, f->x, x, sizeof(double) * n_rows * n_x, hipMemcpyHostToDevice));
+  if (!x || n_rows != f->N || n_x != (f->cfg.n_x > 0 ? f->cfg.n_x : 1)) FAIL(f, LSQAMD_EINVAL, "set_x: shape");
+  HIPCHK(f, copy_sync(f, f->x, x, sizeof(double) * n_rows * n_x, hipMemcpyHostToDevice));
   f->have_x = true;
   return 0;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
@@ -907,7 +1043,7 @@ int lsqamdb_set_x(lsqamdb_fits *f, const double *x, int64_t n_rows, int32_t n_x)
 int lsqamdb_set_tape(lsqamdb_fits *f, const int32_t *code, int32_t n_code, const double *consts, int32_t n_consts) try {
   if (!f) return LSQAMD_EINVAL;
   if (!code || n_code < 1 || n_code > LSQAMD_TAPE_MAX_CODE || n_consts < 0 || n_consts > 1024 || (n_consts > 0 && !consts))
-    BFAIL(f, LSQAMD_EINVAL, "set_tape: sizes");
+    FAIL(f, LSQAMD_EINVAL, "set_tape: sizes");
   {   // stack discipline and operand ranges (the compiled route indexes by them)
     int sp = 0;
     for (int t = 0; t < n_code; ++t) {
@@ -919,9 +1055,9 @@ int lsqamdb_set_tape(lsqamdb_fits *f, const int32_t *code, int32_t n_code, const
       else if (op >= LSQAMD_OP_ADD && op <= LSQAMD_OP_POW) { ok = sp >= 2; --sp; }
       else if (op >= LSQAMD_OP_NEG && op <= LSQAMD_OP_LAST) ok = sp >= 1;
       else ok = false;
-      if (!ok || sp > LSQAMD_TAPE_MAX_STACK) BFAIL(f, LSQAMD_EINVAL, "set_tape: malformed tape at instruction %d", t);
+      if (!ok || sp > LSQAMD_TAPE_MAX_STACK) FAIL(f, LSQAMD_EINVAL, "set_tape: malformed tape at instruction %d", t);
     }
-    if (sp != 1) BFAIL(f, LSQAMD_EINVAL, "set_tape: the tape must leave exactly one value");
+    if (sp != 1) FAIL(f, LSQAMD_EINVAL, "set_tape: the tape must leave exactly one value");
   }
   // the formula compiled (jit.hip): one launch per evaluation with the fits as blockIdx.y, whatever P is -- the
   // interpreter route (forward mode, ceil(P / 16) passes per row) remains for tapes of <= 1024 instructions when
@@ -930,10 +1066,10 @@ int lsqamdb_set_tape(lsqamdb_fits *f, const int32_t *code, int32_t n_code, const
   if (f->jit) lsqamd_jit::release(static_cast<const lsqamd_jit::Kernel *>(f->jit));
   f->jit = lsqamd_jit::compile_tape(code, n_code, consts, n_consts, (int)f->P, f->cfg.n_x > 0 ? f->cfg.n_x : 1, why);
   if (!f->jit && (n_code > 1024 || n_consts > 256))
-    BFAIL(f, LSQAMD_EUNSUPPORTED, "set_tape: %d instructions need the compiled route, which is unavailable (%s)", n_code, why.c_str());
+    FAIL(f, LSQAMD_EUNSUPPORTED, "set_tape: %d instructions need the compiled route, which is unavailable (%s)", n_code, why.c_str());
   if (n_code <= 1024 && n_consts <= 256) {
-    BHIP(f, copy_sync(f, f->tape, code, sizeof(int32_t) * n_code, hipMemcpyHostToDevice));
-    if (n_consts > 0) BHIP(f, copy_sync(f, f->consts, consts, sizeof(double) * n_consts, hipMemcpyHostToDevice));
+    HIPCHK(f, copy_sync(f, f->tape, code, sizeof(int32_t) * n_code, hipMemcpyHostToDevice));
+    if (n_consts > 0) HIPCHK(f, copy_sync(f, f->consts, consts, sizeof(double) * n_consts, hipMemcpyHostToDevice));
   }
   f->n_tape = n_code;
   f->have_tape = true;
@@ -943,8 +1079,8 @@ int lsqamdb_set_tape(lsqamdb_fits *f, const int32_t *code, int32_t n_code, const
 /* shared data: ymean[N], wdiag[N] = 1/sdev of the 1x1 rows */
 int lsqamdb_set_data(lsqamdb_fits *f, const double *ymean, const double *wdiag) try {
   if (!f || !ymean || !wdiag) return LSQAMD_EINVAL;
-  BHIP(f, copy_sync(f, f->ymean, ymean, sizeof(double) * f->N, hipMemcpyHostToDevice));
-  BHIP(f, copy_sync(f, f->wdiag, wdiag, sizeof(double) * f->N, hipMemcpyHostToDevice));
+  HIPCHK(f, copy_sync(f, f->ymean, ymean, sizeof(double) * f->N, hipMemcpyHostToDevice));
+  HIPCHK(f, copy_sync(f, f->wdiag, wdiag, sizeof(double) * f->N, hipMemcpyHostToDevice));
   f->ymean_stride = 0;
   f->have_data = true;
   return 0;
@@ -954,8 +1090,8 @@ int lsqamdb_set_data(lsqamdb_fits *f, const double *ymean, const double *wdiag) 
  * covariance, new means); the whitening set by lsqamdb_set_data / _set_blocks is kept */
 int lsqamdb_set_data_means(lsqamdb_fits *f, const double *ymean) try {
   if (!f || !ymean) return LSQAMD_EINVAL;
-  if (!f->have_data) BFAIL(f, LSQAMD_EINVAL, "set_data_means: call lsqamdb_set_data first");
-  BHIP(f, copy_sync(f, f->ymean, ymean, sizeof(double) * f->B * f->N, hipMemcpyHostToDevice));
+  if (!f->have_data) FAIL(f, LSQAMD_EINVAL, "set_data_means: call lsqamdb_set_data first");
+  HIPCHK(f, copy_sync(f, f->ymean, ymean, sizeof(double) * f->B * f->N, hipMemcpyHostToDevice));
   f->ymean_stride = f->N;
   return 0;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
@@ -964,7 +1100,7 @@ int lsqamdb_set_data_means(lsqamdb_fits *f, const double *ymean) try {
 int lsqamdb_set_blocks(lsqamdb_fits *f, int32_t n_blocks, const int64_t *row0, const int64_t *size,
                        const int64_t *modes, const int32_t *tri, const double *wt) try {
   if (!f) return LSQAMD_EINVAL;
-  if (n_blocks != f->cfg.n_blocks) BFAIL(f, LSQAMD_EINVAL, "set_blocks: n_blocks differs from the config");
+  if (n_blocks != f->cfg.n_blocks) FAIL(f, LSQAMD_EINVAL, "set_blocks: n_blocks differs from the config");
   if (n_blocks == 0) { f->have_blocks = true; return 0; }
   if (!row0 || !size || !modes || !tri || !wt) return LSQAMD_EINVAL;
   std::vector<uint8_t> inb((size_t)f->N, 0);
@@ -977,21 +1113,21 @@ int lsqamdb_set_blocks(lsqamdb_fits *f, int32_t n_blocks, const int64_t *row0, c
   for (int32_t k = 0; k < n_blocks; ++k) {
     if (size[k] < 1 || size[k] > f->cfg.max_block || row0[k] < 0 || row0[k] + size[k] > f->N ||
         modes[k] < 0 || modes[k] > size[k])
-      BFAIL(f, LSQAMD_EINVAL, "set_blocks: block %d out of range", k);
+      FAIL(f, LSQAMD_EINVAL, "set_blocks: block %d out of range", k);
     for (int64_t i = 0; i < size[k]; ++i) {
-      if (inb[(size_t)(row0[k] + i)]) BFAIL(f, LSQAMD_EINVAL, "set_blocks: blocks overlap");
+      if (inb[(size_t)(row0[k] + i)]) FAIL(f, LSQAMD_EINVAL, "set_blocks: blocks overlap");
       inb[(size_t)(row0[k] + i)] = 1;
     }
     woff[(size_t)k] = off;
     off += size[k] * size[k];
   }
-  if (off != f->cfg.sum_block_sq) BFAIL(f, LSQAMD_EINVAL, "set_blocks: sum of squares differs from the config");
+  if (off != f->cfg.sum_block_sq) FAIL(f, LSQAMD_EINVAL, "set_blocks: sum of squares differs from the config");
   f->h_woff = woff;
-  BHIP(f, copy_sync(f, f->in_block, inb.data(), inb.size(), hipMemcpyHostToDevice));
-  BHIP(f, copy_sync(f, f->blk_row0, row0, sizeof(int64_t) * n_blocks, hipMemcpyHostToDevice));
-  BHIP(f, copy_sync(f, f->blk_size, size, sizeof(int64_t) * n_blocks, hipMemcpyHostToDevice));
-  BHIP(f, copy_sync(f, f->blk_woff, woff.data(), sizeof(int64_t) * n_blocks, hipMemcpyHostToDevice));
-  BHIP(f, copy_sync(f, f->wt, wt, sizeof(double) * off, hipMemcpyDefault));   // host or device source
+  HIPCHK(f, copy_sync(f, f->in_block, inb.data(), inb.size(), hipMemcpyHostToDevice));
+  HIPCHK(f, copy_sync(f, f->blk_row0, row0, sizeof(int64_t) * n_blocks, hipMemcpyHostToDevice));
+  HIPCHK(f, copy_sync(f, f->blk_size, size, sizeof(int64_t) * n_blocks, hipMemcpyHostToDevice));
+  HIPCHK(f, copy_sync(f, f->blk_woff, woff.data(), sizeof(int64_t) * n_blocks, hipMemcpyHostToDevice));
+  HIPCHK(f, copy_sync(f, f->wt, wt, sizeof(double) * off, hipMemcpyDefault));   // host or device source
   f->have_blocks = true;
   return 0;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
@@ -1000,9 +1136,9 @@ int lsqamdb_set_blocks(lsqamdb_fits *f, int32_t n_blocks, const int64_t *row0, c
  * P x P precision shared by all fits (copies of a fit differ in their prior means, not its covariance) */
 int lsqamdb_set_priors(lsqamdb_fits *f, const double *mean, const double *prec) try {
   if (!f || !mean || !prec) return LSQAMD_EINVAL;
-  if (!f->cfg.has_prior) BFAIL(f, LSQAMD_EINVAL, "set_priors: config has no prior");
-  BHIP(f, copy_sync(f, f->pmean, mean, sizeof(double) * f->B * f->P, hipMemcpyHostToDevice));
-  BHIP(f, copy_sync(f, f->pprec, prec, sizeof(double) * (f->cfg.prior_dense ? f->P * f->P : f->B * f->P),
+  if (!f->cfg.has_prior) FAIL(f, LSQAMD_EINVAL, "set_priors: config has no prior");
+  HIPCHK(f, copy_sync(f, f->pmean, mean, sizeof(double) * f->B * f->P, hipMemcpyHostToDevice));
+  HIPCHK(f, copy_sync(f, f->pprec, prec, sizeof(double) * (f->cfg.prior_dense ? f->P * f->P : f->B * f->P),
                     hipMemcpyDefault));   // host or device source
   f->have_prior = true;
   return 0;
@@ -1011,9 +1147,9 @@ int lsqamdb_set_priors(lsqamdb_fits *f, const double *mean, const double *prec) 
 int lsqamdb_set_options(lsqamdb_fits *f, const lsqamd_options *opt) try {
   if (!f || !opt) return LSQAMD_EINVAL;
   if (opt->xtol < 0 || opt->gtol < 0 || opt->maxit < 0 || opt->scaler < 0 || opt->scaler > LSQAMD_SCALE_MARQUARDT)
-    BFAIL(f, LSQAMD_EINVAL, "set_options: bad value");
+    FAIL(f, LSQAMD_EINVAL, "set_options: bad value");
   if (opt->trs != LSQAMD_TRS_LM && opt->trs != LSQAMD_TRS_DOGLEG && opt->trs != LSQAMD_TRS_DDOGLEG && opt->trs != LSQAMD_TRS_SUBSPACE2D)
-    BFAIL(f, LSQAMD_EUNSUPPORTED, "set_options: the batched engine runs alg='lm', 'dogleg', 'ddogleg' and 'subspace2D' only");
+    FAIL(f, LSQAMD_EUNSUPPORTED, "set_options: the batched engine runs alg='lm', 'dogleg', 'ddogleg' and 'subspace2D' only");
   f->opt = *opt;
   return 0;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
@@ -1022,215 +1158,83 @@ int lsqamdb_set_options(lsqamdb_fits *f, const lsqamd_options *opt) try {
  * hipGraph after the first eager round and replay it. */
 int lsqamdb_run(lsqamdb_fits *f, const double *p0, lsqamd_summary *summaries, int32_t use_graph) try {
   if (!f || !p0) return LSQAMD_EINVAL;
-  if (!f->have_data || (f->cfg.has_prior && !f->have_prior) || (f->cfg.n_blocks > 0 && !f->have_blocks) ||
-      (f->cfg.model != LSQAMD_MODEL_IDENTITY && !f->have_x) || (f->cfg.model == LSQAMD_MODEL_TAPE && !f->have_tape))
-    BFAIL(f, LSQAMD_EINVAL, "run: inputs missing");
-  const int64_t P = f->P, B = f->B;
+  int rc = inputs_ready(f);
+  if (rc) return rc;
   if (f->timing) use_graph = 0;      // (events around single launches: eager rounds)
   // inputs the caller made on ITS stream (device-resident weights) are complete before the engine's stream reads them.  A null
   // stream is not waited for: synchronising the legacy stream from here would collide with any graph capture another
   // thread has open (see copy_sync); a caller working on the legacy stream orders its own work (include/lsqfit_amd.h)
   if (f->user_st) (void)hipStreamSynchronize(f->user_st);
-  hipEvent_t e0 = lsqamd_host::event_take(), e1 = lsqamd_host::event_take();
-  (void)hipEventRecord(e0, f->st);
-  BHIP(f, hipMemcpyAsync(f->px, p0, sizeof(double) * B * P, hipMemcpyHostToDevice, f->st));
-  {  // everything active for the initial evaluation
-    std::vector<int32_t> ones((size_t)B, 1);
-    BHIP(f, hipMemcpyAsync(f->s.active, ones.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, f->st));
-    BHIP(f, hipStreamSynchronize(f->st));
-  }
-  // Small fits (a compiled formula, <= 12 parameters, <= 4096 uncorrelated rows or <= 256 with covariance blocks): every
-  // fit of the batch is ONE workgroup of ONE launch (jit.hip lsqamd_jit_lmb -- the loop of the single-fit kernel, lm_driver.hip
-  // run_one_launch) instead of ~20 lockstep launches per round.  Any irregular fit sends the whole batch through the
-  // lockstep engine below.  LSQAMD_ONE_LAUNCH_FIT=0 disables.
-  f->one_launch = false;
-  {
-    const char *e = getenv("LSQAMD_ONE_LAUNCH_FIT");
-    const lsqamd_jit::Kernel *k = static_cast<const lsqamd_jit::Kernel *>(f->jit);
-    const bool rows_ok = f->N <= lsqamd_jit::fit_row_limit(k, f->cfg.n_blocks != 0) && f->cfg.n_blocks <= 64;
-    if (!(e && e[0] == '0') && lsqamd_jit::has_batch_fit_kernel(k) && P <= lsqamd_jit::FIT_MAX_P && f->N >= 1 && rows_ok &&
-        f->opt.maxit >= 1 && f->opt.maxit <= 20000 && f->opt.trs == LSQAMD_TRS_LM) {
-      const int64_t red_stride = f->npk + P + 1, w_stride = f->nblk * 128 * 128;
-      lsqamd_jit::FitArgs a;
-      a.x = f->x; a.ymean = f->ymean; a.wdiag = f->wdiag; a.n_data = f->N;
-      a.in_block = f->in_block; a.wt = f->wt;
-      a.blk_row0 = reinterpret_cast<const long long *>(f->blk_row0); a.blk_size = reinterpret_cast<const long long *>(f->blk_size);
-      a.blk_woff = reinterpret_cast<const long long *>(f->blk_woff); a.n_blocks = f->cfg.n_blocks;
-      a.p0 = f->px; a.p = f->px; a.p_trial = f->pxt; a.dscale = f->diag; a.apk = f->red; a.gvec = f->red + f->npk;
-      a.v_out = f->dx; a.coln2 = nullptr; a.st = nullptr;
-      a.prior_prec = f->cfg.has_prior ? f->pprec : nullptr;
-      a.prior_mean = f->cfg.has_prior ? f->pmean : nullptr;
-      a.prior_dense = f->cfg.prior_dense; a.scaler = f->opt.scaler; a.maxit = f->opt.maxit; a.watch = 0;
-      a.xtol = f->opt.xtol; a.gtol = f->opt.gtol; a.factor_up = f->opt.factor_up; a.factor_down = f->opt.factor_down;
-      a.hostptr_bits = 0.0;
-      a.cov = f->cov; a.ldc = f->ldm; a.want_cov = 1; a.pad_ = 0;
-      a.host = f->chol_work;                       // (free until a covariance is asked for: 16384 doubles per fit)
-      a.pub = nullptr; a.seq = 0;                  // (the batch's results are copied after a stream synchronisation)
-      lsqamd_jit::FitBatch bt;
-      bt.ymean_stride = f->ymean_stride; bt.prec_stride = f->cfg.prior_dense ? 0 : P; bt.tile_stride = red_stride;
-      bt.cov_stride = P * f->ldm; bt.scratch_stride = w_stride;
-      bt.logdet = f->logdet; bt.mu = f->s.mu; bt.chi2 = f->s.chi2;
-      bt.nit = f->s.nit; bt.info = f->s.info; bt.status = f->s.status; bt.nfev = f->s.nfev; bt.njev = f->s.njev;
-      bt.active = f->s.active; bt.reason = f->s.bad;
-      BHIP(f, lsqamd_jit::launch_fit_batch(k, f->st, a, bt, (int)B));
-      std::vector<int32_t> reason((size_t)B, 0);
-      BHIP(f, hipMemcpyAsync(reason.data(), f->s.bad, sizeof(int32_t) * B, hipMemcpyDeviceToHost, f->st));
-      BHIP(f, hipStreamSynchronize(f->st));
-      bool all_done = true, all_cov = true;
-      for (int64_t b = 0; b < B; ++b) {
-        all_done = all_done && (reason[(size_t)b] == 1 || reason[(size_t)b] == 3);
-        all_cov = all_cov && reason[(size_t)b] == 1;
-      }
-      if (all_done) {
-        f->one_launch = true;
-        f->rounds = 1;
-        f->graph_used = 0;
-        f->have_cov_from_run = all_cov;
-      } else {   // the lockstep engine from the start: p0 again, every fit active
-        BHIP(f, hipMemcpyAsync(f->px, p0, sizeof(double) * B * P, hipMemcpyHostToDevice, f->st));
-        std::vector<int32_t> ones((size_t)B, 1);
-        BHIP(f, hipMemcpyAsync(f->s.active, ones.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, f->st));
-        BHIP(f, hipStreamSynchronize(f->st));
-      }
-    }
-  }
-  int rc = 0;
-  if (!f->one_launch) {
-  rc = normal_all(f, f->s.active);
-  if (rc) return rc;
-  hipLaunchKernelGGL(b_init_kernel, dim3((unsigned)B), dim3(256), 0, f->st, P, f->T, f->red, f->npk + P + 1,
-                     f->red + f->npk, f->npk + P + 1, f->diag, f->opt.scaler, f->s);
-  if (f->opt.trs != LSQAMD_TRS_LM) {   // the family's trust radius and the legs at p0
-    BHIP(f, launch_trs_init(f->st, P, (int32_t)B, f->diag, f->px, f->t));
-    rc = legs_all(f, f->s.active);
-    if (rc) return rc;
-  }
-  f->rounds = 0;
-  f->graph_used = 0;
-  // kernel arguments (tolerances, maxit, factors) are baked into graph nodes: re-capture per run
-  if (f->gexec) { (void)hipGraphExecDestroy(f->gexec); f->gexec = nullptr; }
-  if (f->graph) { (void)hipGraphDestroy(f->graph); f->graph = nullptr; }
-  int32_t n_active = (int32_t)B;
-  const int64_t max_rounds = (int64_t)(f->opt.maxit > 0 ? f->opt.maxit : 0) * 17 + 1;
-  while (n_active > 0 && f->rounds < max_rounds && f->opt.maxit > 0) {
-    if (use_graph && f->rounds >= 1) {
-      if (!f->gexec) {
-        hipError_t e = hipStreamBeginCapture(f->st, hipStreamCaptureModeThreadLocal);
-        if (e == hipSuccess) {
-          rc = round_any(f);
-          hipGraph_t gr = nullptr;
-          e = hipStreamEndCapture(f->st, &gr);
-          // a capture another thread's activity invalidated makes the captured launches fail too: that is a failed CAPTURE
-          // (nothing ran, nothing changed on the device), not a failed round -- the round below runs eagerly
-          if (rc && e == hipSuccess) return rc;
-          rc = 0;
-          if (e == hipSuccess && gr && hipGraphInstantiate(&f->gexec, gr, nullptr, nullptr, 0) == hipSuccess) {
-            f->graph = gr;
-          } else {
-            if (gr) (void)hipGraphDestroy(gr);
-            f->gexec = nullptr;
-            use_graph = 0;
-            capture_reset(f->st);      // (an invalidated capture leaves the stream unusable until it is reset: common.h)
-          }
-        } else {
-          use_graph = 0;
-        }
-        (void)hipGetLastError();
+  RunSpan span{f};
+  (void)hipEventRecord(span.e0, f->st);
+  if ((rc = start_at(f, p0))) return rc;
+  if ((rc = try_one_launch(f, p0)) < 0) return rc;
+  if (rc == 0) {   // the lockstep engine
+    if ((rc = start_lockstep(f))) return rc;
+    int32_t n_active = f->B;
+    const int64_t max_rounds = (int64_t)(f->opt.maxit > 0 ? f->opt.maxit : 0) * 17 + 1;
+    while (n_active > 0 && f->rounds < max_rounds && f->opt.maxit > 0) {
+      if (use_graph && f->rounds >= 1 && !f->gexec) {   // (the first round is eager)
+        if ((rc = capture_round(f))) return rc;
+        if (!f->gexec) use_graph = 0;
       }
       if (f->gexec) {
-        BHIP(f, hipGraphLaunch(f->gexec, f->st));
+        HIPCHK(f, hipGraphLaunch(f->gexec, f->st));
         f->graph_used += 1;
-      } else {
-        rc = round_any(f);
-        if (rc) return rc;
+      } else if ((rc = round_any(f))) {
+        return rc;
       }
-    } else {
-      rc = round_any(f);
-      if (rc) return rc;
+      f->rounds += 1;
+      HIPCHK(f, hipMemcpyAsync(&n_active, f->s.n_active, sizeof(int32_t), hipMemcpyDeviceToHost, f->st));
+      HIPCHK(f, hipStreamSynchronize(f->st));
     }
-    f->rounds += 1;
-    BHIP(f, hipMemcpyAsync(&n_active, f->s.n_active, sizeof(int32_t), hipMemcpyDeviceToHost, f->st));
-    BHIP(f, hipStreamSynchronize(f->st));
   }
-  }   // (!one_launch)
-  (void)hipEventRecord(e1, f->st);
-  (void)hipEventSynchronize(e1);
+  (void)hipEventRecord(span.e1, f->st);
+  (void)hipEventSynchronize(span.e1);
   float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  lsqamd_host::event_give(e0);
-  lsqamd_host::event_give(e1);
+  (void)hipEventElapsedTime(&ms, span.e0, span.e1);
   f->ran = true;
   f->have_cov = f->one_launch && f->have_cov_from_run;     // (the one-launch kernel leaves covariances and log dets behind)
-  if (summaries) {
-    // the per-fit scalars lie one after the other in the workspace (carve_b: s.mu .. s.njev): ONE copy instead of seven
-    const char *lo = reinterpret_cast<const char *>(f->s.mu), *hi = reinterpret_cast<const char *>(f->s.njev + B);
-    std::vector<char> span((size_t)(hi - lo));
-    BHIP(f, copy_sync(f, span.data(), lo, span.size(), hipMemcpyDeviceToHost));
-    auto at = [&](const void *dev) { return span.data() + (reinterpret_cast<const char *>(dev) - lo); };
-    const double *mu = reinterpret_cast<const double *>(at(f->s.mu)), *chi2 = reinterpret_cast<const double *>(at(f->s.chi2));
-    const int32_t *nit = reinterpret_cast<const int32_t *>(at(f->s.nit)), *info = reinterpret_cast<const int32_t *>(at(f->s.info));
-    const int32_t *status = reinterpret_cast<const int32_t *>(at(f->s.status)), *nfev = reinterpret_cast<const int32_t *>(at(f->s.nfev));
-    const int32_t *njev = reinterpret_cast<const int32_t *>(at(f->s.njev));
-    for (int64_t b = 0; b < B; ++b) {
-      lsqamd_summary &s = summaries[b];
-      std::memset(&s, 0, sizeof(s));
-      s.status = status[b] == -2 ? LSQAMD_EMAXITER : status[b];
-      s.info = info[b];
-      s.stopping_criterion = (info[b] >= 0 && info[b] <= 3) ? info[b] : (info[b] == 27 ? 4 : 0);
-      s.nit = nit[b]; s.nfev = nfev[b]; s.njev = njev[b]; s.ntrial = nfev[b] - 1;
-      s.chi2 = chi2[b]; s.mu = mu[b];
-      s.logdet_jtj = NAN;
-      s.t_run_ms = ms;
-      s.t_setup_ms = (double)f->graph_used;  // rounds replayed from the captured graph
-    }
-  }
-  return 0;
+  return summaries ? write_summaries(f, summaries, ms) : 0;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
 
 int lsqamdb_get_x(lsqamdb_fits *f, double *out, size_t cap) try {
   if (!f || !out) return LSQAMD_EINVAL;
-  if (cap < (size_t)(f->B * f->P)) BFAIL(f, LSQAMD_ECAPACITY, "get_x: need %lld", (long long)(f->B * f->P));
-  BHIP(f, copy_sync(f, out, f->px, sizeof(double) * f->B * f->P, hipMemcpyDeviceToHost));
+  if (cap < (size_t)(f->B * f->P)) FAIL(f, LSQAMD_ECAPACITY, "get_x: need %lld", (long long)(f->B * f->P));
+  HIPCHK(f, copy_sync(f, out, f->px, sizeof(double) * f->B * f->P, hipMemcpyDeviceToHost));
   return 0;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
 
 /* (J^T J)^-1 of every fit at its final point + log det(J^T J); results stay on the device */
 int lsqamdb_covariance(lsqamdb_fits *f, double *logdet_out, size_t cap) try {
   if (!f) return LSQAMD_EINVAL;
-  if (!f->ran) BFAIL(f, LSQAMD_EINVAL, "covariance: run first");
-  if (f->have_cov && f->one_launch) {     // formed by the fit kernel itself
-    if (logdet_out) {
-      if (cap < (size_t)f->B) BFAIL(f, LSQAMD_ECAPACITY, "covariance: need %lld", (long long)f->B);
-      BHIP(f, copy_sync(f, logdet_out, f->logdet, sizeof(double) * f->B, hipMemcpyDeviceToHost));
-    }
-    return 0;
+  if (!f->ran) FAIL(f, LSQAMD_EINVAL, "covariance: run first");
+  const int64_t P = f->P;
+  const int32_t B = f->B;
+  if (!(f->have_cov && f->one_launch)) {     // (else: formed by the fit kernel itself)
+    // the first half of factor_and_solve's chain on its own: P columns instead of ncols_aug, no right-hand side, no mask
+    hipLaunchKernelGGL(b_build_damped_kernel, dim3((unsigned)f->ntile, 16, (unsigned)B), dim3(256), 0, f->st, f->red,
+                       f->red_stride, P, f->T, f->ldm, f->s.mu, f->diag, (const double *)nullptr, f->red_stride, f->M,
+                       f->m_stride, (const int32_t *)nullptr, 0);
+    HIPCHK(f, potrf_upper_batched(f->st, f->M, P, f->ldm, P, f->chol_work, f->s.cholinfo, B, f->m_stride, f->w_stride, nullptr));
+    hipLaunchKernelGGL(b_logdiag_kernel, dim3((unsigned)B), dim3(256), 0, f->st, f->M, f->m_stride, P, f->ldm, f->logdet);
+    HIPCHK(f, trtri_upper_to_lower_T_batched(f->st, f->M, P, f->ldm, f->chol_work, f->Wl, f->ldm, B, f->m_stride, f->w_stride,
+                                             f->m_stride));
+    GemmTN g;
+    g.X = f->Wl; g.Y = f->Wl; g.ldx = g.ldy = f->ldm; g.sx = g.sy = f->m_stride;
+    g.C = f->cov; g.ldc = f->ldm; g.sc = f->m_stride;
+    g.M = P; g.N = P; g.K = P;
+    g.upper_only = 1; g.xy_lower_tri = 1;
+    g.batch = B;
+    HIPCHK(f, launch_gemm_tn(f->st, g));
+    hipLaunchKernelGGL(b_symmetrize_kernel, dim3((unsigned)((P + 255) / 256), (unsigned)P, (unsigned)B), dim3(256), 0,
+                       f->st, f->cov, f->m_stride, P, f->ldm);
+    HIPCHK(f, hipStreamSynchronize(f->st));
+    f->have_cov = true;
   }
-  const int64_t P = f->P, B = f->B, m_stride = P * f->ldm, w_stride = f->nblk * 128 * 128;
-  const int64_t red_stride = f->npk + P + 1;
-  const unsigned ntile = (unsigned)(f->T * (f->T + 1) / 2);
-  hipLaunchKernelGGL(b_build_damped_kernel, dim3(ntile, 16, (unsigned)B), dim3(256), 0, f->st, f->red,
-                     red_stride, P, f->T, f->ldm, f->s.mu, f->diag, (const double *)nullptr, red_stride, f->M,
-                     m_stride, (const int32_t *)nullptr, 0);
-  BHIP(f, potrf_upper_batched(f->st, f->M, P, f->ldm, P, f->chol_work, f->s.cholinfo, (int32_t)B, m_stride,
-                              w_stride, nullptr));
-  hipLaunchKernelGGL(b_logdiag_kernel, dim3((unsigned)B), dim3(256), 0, f->st, f->M, m_stride, P, f->ldm,
-                     f->logdet);
-  BHIP(f, trtri_upper_to_lower_T_batched(f->st, f->M, P, f->ldm, f->chol_work, f->Wl, f->ldm, (int32_t)B,
-                                         m_stride, w_stride, m_stride));
-  GemmTN g;
-  g.X = f->Wl; g.Y = f->Wl; g.ldx = g.ldy = f->ldm; g.sx = g.sy = m_stride;
-  g.C = f->cov; g.ldc = f->ldm; g.sc = m_stride;
-  g.M = P; g.N = P; g.K = P;
-  g.upper_only = 1; g.xy_lower_tri = 1;
-  g.batch = (int32_t)B;
-  BHIP(f, launch_gemm_tn(f->st, g));
-  hipLaunchKernelGGL(b_symmetrize_kernel, dim3((unsigned)((P + 255) / 256), (unsigned)P, (unsigned)B), dim3(256), 0,
-                     f->st, f->cov, m_stride, P, f->ldm);
-  BHIP(f, hipStreamSynchronize(f->st));
-  f->have_cov = true;
   if (logdet_out) {
-    if (cap < (size_t)B) BFAIL(f, LSQAMD_ECAPACITY, "covariance: need %lld", (long long)B);
-    BHIP(f, copy_sync(f, logdet_out, f->logdet, sizeof(double) * B, hipMemcpyDeviceToHost));
+    if (cap < (size_t)B) FAIL(f, LSQAMD_ECAPACITY, "covariance: need %lld", (long long)B);
+    HIPCHK(f, copy_sync(f, logdet_out, f->logdet, sizeof(double) * B, hipMemcpyDeviceToHost));
   }
   return 0;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
@@ -1238,12 +1242,12 @@ int lsqamdb_covariance(lsqamdb_fits *f, double *logdet_out, size_t cap) try {
 int lsqamdb_get_cov(lsqamdb_fits *f, int32_t fit, double *out, size_t cap) try {
   if (!f || !out || fit < 0 || fit >= f->B) return LSQAMD_EINVAL;
   const int64_t P = f->P;
-  if (cap < (size_t)(P * P)) BFAIL(f, LSQAMD_ECAPACITY, "get_cov: need %lld", (long long)(P * P));
+  if (cap < (size_t)(P * P)) FAIL(f, LSQAMD_ECAPACITY, "get_cov: need %lld", (long long)(P * P));
   if (!f->have_cov) {
     const int rc = lsqamdb_covariance(f, nullptr, 0);
     if (rc) return rc;
   }
-  BHIP(f, copy2d_sync(f, out, sizeof(double) * P, f->cov + (int64_t)fit * P * f->ldm, sizeof(double) * f->ldm,
+  HIPCHK(f, copy2d_sync(f, out, sizeof(double) * P, f->cov + (int64_t)fit * P * f->ldm, sizeof(double) * f->ldm,
                       sizeof(double) * P, (size_t)P, hipMemcpyDeviceToHost));
   return 0;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
@@ -1251,13 +1255,13 @@ int lsqamdb_get_cov(lsqamdb_fits *f, int32_t fit, double *out, size_t cap) try {
 int lsqamdb_get_cov_all(lsqamdb_fits *f, double *out, size_t cap) try {
   if (!f || !out) return LSQAMD_EINVAL;
   const int64_t P = f->P, B = f->B;
-  if (cap < (size_t)(B * P * P)) BFAIL(f, LSQAMD_ECAPACITY, "get_cov_all: need %lld", (long long)(B * P * P));
+  if (cap < (size_t)(B * P * P)) FAIL(f, LSQAMD_ECAPACITY, "get_cov_all: need %lld", (long long)(B * P * P));
   if (!f->have_cov) {
     const int rc = lsqamdb_covariance(f, nullptr, 0);
     if (rc) return rc;
   }
   // fit b's rows follow fit b - 1's in f->cov (P rows of ldm doubles each): one strided copy of B * P rows
-  BHIP(f, copy2d_sync(f, out, sizeof(double) * P, f->cov, sizeof(double) * f->ldm, sizeof(double) * P, (size_t)(B * P),
+  HIPCHK(f, copy2d_sync(f, out, sizeof(double) * P, f->cov, sizeof(double) * f->ldm, sizeof(double) * P, (size_t)(B * P),
                       hipMemcpyDeviceToHost));
   return 0;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
@@ -1288,13 +1292,8 @@ int lsqamdb_timing_enable(lsqamdb_fits *f, int32_t on) try {
   if (!f) return LSQAMD_EINVAL;
   (void)hipStreamSynchronize(f->st);
   f->timing = on != 0;
-  for (auto *v : {&f->tm_syrk, &f->tm_chol}) {
-    for (auto &pr : *v) {
-      lsqamd_host::event_give(pr.first);
-      lsqamd_host::event_give(pr.second);
-    }
-    v->clear();
-  }
+  give_events(f->tm_syrk, f->dev);
+  give_events(f->tm_chol, f->dev);
   return 0;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
 

@@ -134,3 +134,39 @@ def test_batched_fits_of_a_compiled_tape_model(amd):
     print('batched tape model: %.1f ms on device, cosmix kernels %.1f ms' % (ob['device_ms'], oa['device_ms']))
     a.close()
     b.close()
+
+
+def test_batched_timing_brackets(amd):
+    """The timing branch of the lockstep engine: with the timers on, rounds run eagerly, the J^T J launch is bracketed once
+    per normal_all (one at p0, one per round) and the LM factorisation once per round; the dogleg family's legs factorise
+    outside any bracket.  An eager round and a replayed one run the same kernels in the same order (no float atomics), so the
+    timed run reproduces the graph run bit for bit."""
+    d, pmb, psb = make(256, 16, 4, 52)
+    bf = amd.BatchedFits(d['model'], d['x'], d['ymean'], d['yerr'], pmb, psb)
+    p0 = np.tile(d['p0'], (4, 1))
+    p0[1] += 0.02
+    out0 = bf.run(p0=p0, use_graph=True)
+    assert out0['graph_rounds'] > 0
+    bf.timing(True)
+    out1 = bf.run(p0=p0, use_graph=True)
+    tm = bf.timings()
+    print('timed lm run: %d rounds, %r' % (out1['rounds'], tm))
+    assert out1['graph_rounds'] == 0
+    assert tm['syrk'][1] == out1['rounds'] + 1
+    assert tm['cholesky'][1] == out1['rounds']
+    assert tm['syrk'][0] > 0 and tm['cholesky'][0] > 0
+    for key in ('pmean', 'chi2', 'nit', 'nfev', 'stopping_criterion'):
+        assert np.array_equal(out1[key], out0[key]), key
+    bf.timing(True)                                # (clears the counters)
+    out2 = bf.run(p0=p0, use_graph=True, alg='dogleg')
+    tm = bf.timings()
+    print('timed dogleg run: %d rounds, %r' % (out2['rounds'], tm))
+    assert out2['graph_rounds'] == 0
+    assert tm['syrk'][1] == out2['rounds'] + 1
+    assert tm['cholesky'][1] == 0
+    bf.timing(False)
+    tm = bf.timings()
+    assert tm['syrk'][1] == 0 and tm['cholesky'][1] == 0
+    out3 = bf.run(p0=p0, use_graph=True)
+    assert out3['graph_rounds'] > 0
+    bf.close()
