@@ -581,16 +581,12 @@ int lsqamd_step(lsqamd_fit *f, int32_t *info) try {
   if (const int rcd = device_ok(f)) return rcd;
   if (!f->initialised) FAIL(f, LSQAMD_EINVAL, "lsqamd_step before lsqamd_init");
   if (f->opt.trs >= LSQAMD_TRS_TRF) FAIL(f, LSQAMD_EUNSUPPORTED, "lsqamd_step: the scipy-plugin methods (trf, dogbox, minpack lm) run through lsqamd_run only");
-  const int rc = iterate(f);
+  int met = 0;
+  const int rc = driver_iteration(f, &met, true);
   if (rc < 0) return rc;
-  f->nit++;
   if (f->timing) resolve_timers(f, true);
-  if (rc == LSQAMD_ENOPROG) {
-    if (info) *info = LSQAMD_ENOPROG;
-    return LSQAMD_ENOPROG;
-  }
-  if (info) *info = convergence_test(f);
-  return 0;
+  if (info) *info = met;
+  return rc;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
 
 int lsqamd_finish(lsqamd_fit *f, lsqamd_summary *out) try {
@@ -604,6 +600,40 @@ int lsqamd_finish(lsqamd_fit *f, lsqamd_summary *out) try {
   return rc == LSQAMD_ENOTPD ? 0 : rc;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
 
+// After a fit with a robust loss (cov_rc: what its covariance came to).  That covariance is the loss-scaled Jacobian's, which
+// scipy returns (src/lsqfit/_scipy.py:165-169); chi2 and log det(J^T J) -- and what the getters hand out from here on -- are
+// those of the TRUE residuals and Jacobian at the fit point (:160-161, src/lsqfit/__init__.py:667,:719): one more
+// evaluation, without the loss
+static int true_residual_state(lsqamd_fit *f, int cov_rc) {
+  const int32_t loss = f->loss;
+  f->loss = LSQAMD_LOSS_LINEAR;
+  int r2 = eval_normal_dev(f, f->p_dev, true);
+  if (r2 == 0) r2 = logdet_normal(f);
+  f->loss = loss;
+  f->njev--;                      // (bookkeeping of the library, not an evaluation of the method)
+  if (r2 < 0 && r2 != LSQAMD_ENOTPD) return r2;
+  // (the evaluation above overwrote the loss-scaled normal matrix: the covariance in f->cov stays valid only if it was
+  // made; a later lsqamd_get_cov must not recompute it from the UNSCALED matrix that is there now)
+  f->have_cov = cov_rc == 0;
+  f->cov_unavailable = cov_rc != 0;
+  return 0;
+}
+
+// t_run_ms of a run that began at event a (cov_rc: what its covariance came to); frees the staging arena once nothing runs
+static float run_elapsed_ms(lsqamd_fit *f, hipEvent_t a, hipEvent_t b, int cov_rc) {
+  float ms = 0.f;
+  if (f->used_one_launch && f->have_cov && cov_rc == 0) {
+    // the whole run was the one kernel whose last word the host has already seen: nothing is left on the stream to wait for
+    // (an event synchronisation is ~15 us of sleeping and waking); the kernel timed itself (100 MHz ticks)
+    ms = (float)(f->fit_rec[(size_t)lsqamd_jit::fit_host_diag((int)f->P) + 4] * 1e-5);
+    f->stage_off = 0;
+  } else {
+    (void)hipEventRecord(b, f->st);
+    if (hipEventSynchronize(b) == hipSuccess) f->stage_off = 0;
+    (void)hipEventElapsedTime(&ms, a, b);
+  }
+  return ms;
+}
 
 int lsqamd_run(lsqamd_fit *f, const double *p0, lsqamd_summary *out) try {
   if (!f || !p0) return LSQAMD_EINVAL;
@@ -616,77 +646,19 @@ int lsqamd_run(lsqamd_fit *f, const double *p0, lsqamd_summary *out) try {
   (void)hipEventRecord(ev.a, f->st);
   f->used_one_launch = false;
   f->cov_host_valid = false;
-  int rc = 0;
-  int iter = 0, info = 0, status = -2;
-  bool early = false;
-  const int maxit = f->opt.maxit;
-  if (f->opt.trs >= LSQAMD_TRS_TRF) {
-    int st = 0;
-    if (f->loss != LSQAMD_LOSS_LINEAR && f->opt.trs == LSQAMD_TRS_MINPACK_LM)
-      FAIL(f, LSQAMD_EINVAL, "method='lm' supports only 'linear' loss function.");      // scipy's wording
-    if (f->robust() && f->cfg.has_prior)
-      FAIL(f, LSQAMD_EUNSUPPORTED, "a robust loss acts on residual rows: pass the prior as rows (lsqamd_set_param_rows), not through lsqamd_set_prior");
-    if (f->robust() && (f->comm || f->reduce))
-      FAIL(f, LSQAMD_EUNSUPPORTED, "robust losses are single-rank");
-    rc = f->opt.trs == LSQAMD_TRS_TRF ? run_trf(f, p0, &st)
-         : f->opt.trs == LSQAMD_TRS_DOGBOX ? run_dogbox(f, p0, &st) : run_minpack(f, p0, &st);
-    if (rc) return rc;
-    f->nit = f->nfev;                      // _scipy.py:161: nit = number of function evaluations
-    info = LSQAMD_INFO_TRF + st;
-    status = 0;
-  } else if ((rc = run_one_launch(f, p0, &iter, &info)) != 0) {
-    if (rc < 0) return rc;
-    status = info ? 0 : (iter >= maxit ? LSQAMD_EMAXITER : -2);
-  } else if ((rc = do_init(f, p0)) != 0) {
-    return rc;
-  } else if (maxit > 0) {  // gsl_multifit_nlinear_driver
-    do {
-      rc = iterate(f);
-      if (rc < 0) return rc;
-      f->nit++;
-      if (rc == LSQAMD_ENOPROG && iter == 0) {
-        info = LSQAMD_ENOPROG;
-        status = LSQAMD_EMAXITER;
-        early = true;
-        break;
-      }
-      ++iter;
-      info = convergence_test(f);
-      status = info ? 0 : -2;
-    } while (status == -2 && iter < maxit);
-    if (!early && iter >= maxit && status != 0) status = LSQAMD_EMAXITER;
-  } else {
-    status = 0;
-  }
+  // the method from p0 to its end: one of scipy's three, the whole fit in one launch, or GSL's driver loop on the host
+  int rc = 0, info = 0, status = -2;
+  if (f->opt.trs >= LSQAMD_TRS_TRF) rc = run_scipy_method(f, p0, &status, &info);
+  else if ((rc = run_one_launch(f, p0, &status, &info)) == 0) rc = run_gsl_driver(f, p0, &status, &info);
+  else if (rc > 0) rc = 0;
+  if (rc) return rc;
   rc = (f->used_one_launch && f->have_cov) ? 0 : do_covariance(f);
   if (rc < 0 && rc != LSQAMD_ENOTPD) return rc;
   if (f->robust()) {
-    // the covariance above is that of the loss-scaled Jacobian scipy returns (src/lsqfit/_scipy.py:165-169); chi2 and
-    // log det(J^T J) -- and what the getters hand out from here on -- are those of the TRUE residuals and Jacobian
-    // at the fit point (:160-161, src/lsqfit/__init__.py:667,:719): one more evaluation, without the loss
-    const int32_t loss = f->loss;
-    f->loss = LSQAMD_LOSS_LINEAR;
-    int r2 = eval_normal_dev(f, f->p_dev, true);
-    if (r2 == 0) r2 = logdet_normal(f);
-    f->loss = loss;
-    f->njev--;                      // (bookkeeping of the library, not an evaluation of the method)
-    if (r2 < 0 && r2 != LSQAMD_ENOTPD) return r2;
-    // (the evaluation above overwrote the loss-scaled normal matrix: the covariance in f->cov stays valid only if it was
-    // made; a later lsqamd_get_cov must not recompute it from the UNSCALED matrix that is there now)
-    f->have_cov = rc == 0;
-    f->cov_unavailable = rc != 0;
+    const int r2 = true_residual_state(f, rc);
+    if (r2) return r2;
   }
-  float ms = 0.f;
-  if (f->used_one_launch && f->have_cov && rc == 0) {
-    // the whole run was the one kernel whose last word the host has already seen: nothing is left on the stream to wait for
-    // (an event synchronisation is ~15 us of sleeping and waking); the kernel timed itself (100 MHz ticks)
-    ms = (float)(f->fit_rec[(size_t)lsqamd_jit::fit_host_diag((int)f->P) + 4] * 1e-5);
-    f->stage_off = 0;
-  } else {
-    (void)hipEventRecord(ev.b, f->st);
-    if (hipEventSynchronize(ev.b) == hipSuccess) f->stage_off = 0;   // (the stream has drained: the staging arena is free again)
-    (void)hipEventElapsedTime(&ms, ev.a, ev.b);
-  }
+  const float ms = run_elapsed_ms(f, ev.a, ev.b, rc);
   if (f->timing) resolve_timers(f);
   if (const int rcx = exchange_timeout_check(f)) return rcx;
   fill_summary(f, out, status, info);

@@ -300,12 +300,17 @@ int symv_host(lsqamd_fit *f, const double *x, double *y);
 // f, J, A, g, D, mu, delta at p0 (gsl_multifit_nlinear_init); nfev = njev = 1
 int do_init(lsqamd_fit *f, const double *p0);
 void scale_update(lsqamd_fit *f);
+// a trial point in every host-driven method (lm_driver.hip): x_host -> the device vector dst_dev (p_trial, p_dev) through the
+// pinned staging vector, queued only; ... to p_trial and chi2 there (one nfev); p_trial becomes the current point -- J, A, g,
+// chi2 there (one njev), hx = x_new, the buffers swapped, D updated if rescale (hdx is the caller's)
+int upload_point(lsqamd_fit *f, double *dst_dev, const double *x_host);
+int trial_residual(lsqamd_fit *f, const double *x_host, double *chi2);
+int accept_trial(lsqamd_fit *f, const std::vector<double> &x_new, bool rescale);
 double dot_h(const std::vector<double> &a, const std::vector<double> &b);
 double scaled_norm(const std::vector<double> &d, const std::vector<double> &v);
 
-// ---- scipy_least_squares' methods (scipy_methods.hip); *status_out in scipy's numbering --------
-int run_trf(lsqamd_fit *f, const double *p0, int *status_out);
-int run_dogbox(lsqamd_fit *f, const double *p0, int *status_out);
-int run_minpack(lsqamd_fit *f, const double *p0, int *status_out);
+// ---- scipy_least_squares' methods (scipy_methods.hip): trf, dogbox or MINPACK's lm from p0, after the refusals they share.
+// *status 0, *info LSQAMD_INFO_TRF + scipy's status; nit = nfev (_scipy.py:161)
+int run_scipy_method(lsqamd_fit *f, const double *p0, int *status, int *info);
 
 }  // namespace lsqamd_host

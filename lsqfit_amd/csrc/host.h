@@ -1,5 +1,5 @@
 // Internal to the host side of the single-fit library: what pool.hip, workspace.hip, eval.hip, lm_driver.hip and api.hip
-// share besides the handle itself (fit_state.h, which scipy_methods.hip, qr.hip, rankdef.hip and comm.hip see too).
+// share besides the handle itself (fit_state.h, which qr.hip, rankdef.hip and comm.hip see too; scipy_methods.hip: DBL_EPS).
 // One-line predicates of the hot host path are inline here: a half step of a small fit is ~27 us, and none of them may
 // turn into a call across translation units.  Not part of the C ABI.
 #pragma once
@@ -11,6 +11,7 @@ namespace lsqamd_host {
 
 constexpr int64_t ALIGN = 256;
 constexpr int NRM_BLOCKS = 1024;   // workgroups of the fused normal-equation kernel (few parameters, jit.hip)
+constexpr double DBL_EPS = 2.220446049250313e-16;   // machine epsilon (GSL_DBL_EPSILON, numpy's finfo(float).eps, MINPACK's epsmch)
 inline int64_t rup(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
 struct Carver {   // hands out 256-byte aligned pieces of one device block (dry: only adds the sizes up)
@@ -72,8 +73,12 @@ void note_accept_replayed(lsqamd_fit *f);
 // ---- lm_driver.hip -------------------------------------------------------------------------------------------------
 int iterate(lsqamd_fit *f);             // one trust_iterate: 0 or LSQAMD_ENOPROG; negative on backend failure
 int convergence_test(lsqamd_fit *f);
+// iterate, nit, convergence test -> 0 and *info; an iteration without progress -> LSQAMD_ENOPROG (*info too) when stall_ends
+int driver_iteration(lsqamd_fit *f, int *info, bool stall_ends);
 void fill_summary(lsqamd_fit *f, lsqamd_summary *s, int status, int info);
-// a whole small fit in ONE launch -> 1: done; 0: not this fit's route (the general path runs it); < 0: error
-int run_one_launch(lsqamd_fit *f, const double *p0, int *iter, int *info);
+// The two ways a GSL-method fit runs from p0; *status / *info: what lsqamd_run reports (fill_summary).
+// A whole small fit in ONE launch -> 1: done; 0: not this fit's route (the general path runs it); < 0: error
+int run_one_launch(lsqamd_fit *f, const double *p0, int *status, int *info);
+int run_gsl_driver(lsqamd_fit *f, const double *p0, int *status, int *info);   // do_init + the driver loop: 0 or an error
 
 }  // namespace lsqamd_host

@@ -46,9 +46,13 @@ constexpr int FIT_MAX_ROWS = 8192, FIT_MAX_BLOCK_ROWS = 256;
 // must fit one such chunk)
 constexpr int FIT_MAX_P = 32;
 constexpr int fit_wide_rows(int P) { return P <= 20 ? 256 : 128; }
-// record block of a fit with P parameters: [24, 24 + 5 (P + 1)) x g D coln2 v, then 8 (five cycle counters: developer
-// diagnostics), then the covariance (P x P)
-constexpr int fit_host_diag(int P) { return 24 + 5 * (P + 1); }
+// record block of a fit with P parameters (FitArgs::host): the LM record [0, 16), then the words named here -- why the kernel
+// stopped (1 done, 2 hand the fit to the general path; in a PUBLISHED block this word is fit_flag()), the four counters, 1 when
+// the covariance was formed, its log det(J^T J + prior), the published block's checksum (unused on the device) -- then the
+// mirrors [24, 24 + 5 (P + 1)) x g D coln2 v, then 8 (five cycle counters: developer diagnostics), then the covariance (P x P)
+constexpr int FIT_REC_REASON = 16, FIT_REC_NIT = 17, FIT_REC_NFEV = 18, FIT_REC_NJEV = 19, FIT_REC_NTRIAL = 20, FIT_REC_HAVE_COV = 21,
+              FIT_REC_LOGDET = 22, FIT_REC_CHECK = 23, FIT_REC_MIRRORS = 24;
+constexpr int fit_host_diag(int P) { return FIT_REC_MIRRORS + 5 * (P + 1); }
 constexpr int fit_host_cov(int P) { return fit_host_diag(P) + 8; }
 constexpr int FIT_HOST_DOUBLES = fit_host_cov(FIT_MAX_P) + FIT_MAX_P * FIT_MAX_P;
 struct FitArgs {
@@ -74,7 +78,7 @@ struct FitArgs {
 inline unsigned long long fit_checksum(const unsigned long long *w, int n_words, unsigned long long seq) {
   unsigned long long acc = seq * 0xD6E8FEB86659FD93ull;
   for (int i = 0; i < n_words; ++i)
-    if (i != 16 && i != 23) acc += (w[i] ^ 0x9E3779B97F4A7C15ull) * (2ull * (unsigned long long)i + 1ull);
+    if (i != FIT_REC_REASON && i != FIT_REC_CHECK) acc += (w[i] ^ 0x9E3779B97F4A7C15ull) * (2ull * (unsigned long long)i + 1ull);
   return acc;
 }
 inline unsigned long long fit_flag(int reason, int info, int nit, unsigned long long seq) {

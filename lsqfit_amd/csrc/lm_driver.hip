@@ -5,10 +5,12 @@
 // (eval.hip); the host keeps only O(P) vectors (x, g, D, dx) and the scalars (mu, nu, rho), so that every rank of a
 // row-sharded fit takes identical decisions from the identical all-reduced (J^T J, J^T f, chi2).  Nothing is uploaded
 // inside a step (D and the trial point are mirrored / formed on the device); one stream synchronisation per trial step
-// and one per Jacobian.  Here: the start of a fit (do_init), one trust_iterate for every method (iterate: lm, lmaccel,
-// dogleg, ddogleg, subspace2D on the host; iterate_device: plain lm with its state on the device, its half steps replayed
-// from captured graphs, their records polled from pinned memory; iterate_varpro: linear parameters projected out), the
-// convergence test, the summary, and the whole small fit in one launch (run_one_launch).
+// and one per Jacobian.  Here: what every host-driven method does with a trial point (upload_point, trial_residual,
+// accept_trial; scipy_methods.hip uses them too), the start of a fit (do_init), one trust_iterate for every method (iterate:
+// a step proposed -- propose_lm, propose_legs -- then evaluated and accepted or rejected, for lm, lmaccel, dogleg, ddogleg,
+// subspace2D on the host; iterate_device: plain lm with its state on the device, its half steps replayed from captured graphs,
+// their records polled from pinned memory; iterate_varpro: linear parameters projected out), the convergence test, the driver
+// loop (driver_iteration, run_gsl_driver), the summary, and the whole small fit in one launch (run_one_launch).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -163,7 +165,7 @@ int legs_subspace(lsqamd_fit *f, Legs &L) {
   double r = 0.0;
   for (int64_t j = 0; j < P; ++j) { L.q1[j] -= c * L.q0[j]; r += L.q1[j] * L.q1[j]; }
   r = std::sqrt(r);
-  if (!(r > 20.0 * (double)(P + 2) * 2.220446049250313e-16)) {  // gsl_linalg_QRPT_rank default tolerance
+  if (!(r > 20.0 * (double)(P + 2) * DBL_EPS)) {  // gsl_linalg_QRPT_rank default tolerance
     L.sub = 0;
     return 0;
   }
@@ -217,6 +219,52 @@ int legs_step(lsqamd_fit *f, Legs &L, std::vector<double> &dx) {
   return 0;
 }
 
+// ---- what every host-driven method does with a trial point (declared in fit_state.h: scipy_methods.hip too) ----
+// x_host -> the device vector dst_dev (p_trial; p_dev for a start) through the pinned staging vector.  Queued only
+int upload_point(lsqamd_fit *f, double *dst_dev, const double *x_host) {
+  std::memcpy(f->pin_x, x_host, sizeof(double) * f->P);
+  HIPCHK(f, hipMemcpyAsync(dst_dev, f->pin_x, sizeof(double) * f->P, hipMemcpyHostToDevice, f->st));
+  return 0;
+}
+
+// x_host becomes the trial point (p_trial); chi2 there.  Counts one nfev
+int trial_residual(lsqamd_fit *f, const double *x_host, double *chi2) {
+  const int rc = upload_point(f, f->p_trial, x_host);
+  return rc ? rc : eval_residual_dev(f, f->p_trial, chi2);
+}
+
+// The trial point (x_new on the host, p_trial on the device) becomes the current one: J, A, g, chi2 there (one njev), the
+// buffers swapped, D updated where the method rescales.  hdx stays with the caller: its sign and timing differ per method
+int accept_trial(lsqamd_fit *f, const std::vector<double> &x_new, bool rescale) {
+  const int rc = eval_normal_dev(f, f->p_trial);
+  if (rc) return rc;
+  f->hx = x_new;
+  std::swap(f->p_dev, f->p_trial);
+  if (rescale) scale_update(f);
+  return 0;
+}
+
+// trust_eval_step's rho: actual over predicted reduction, pred_num = the predicted one times chi2_cur.  -1 rejects
+// (NaN-safe: anything but a smaller |f| does)
+static double gain_ratio(double chi2_cur, double chi2_trial, double pred_num) {
+  const double normf = std::sqrt(chi2_cur), normf_t = std::sqrt(chi2_trial);
+  if (!(normf_t < normf)) return -1.0;
+  const double u = normf_t / normf;
+  const double pred = pred_num / chi2_cur;
+  return pred > 0.0 ? (1.0 - u * u) / pred : -1.0;
+}
+
+// nielsen.c: the damping after an accepted and after a rejected trial
+static void nielsen_accept(lsqamd_fit *f, double rho) {
+  const double b = 2.0 * rho - 1.0;
+  f->mu *= std::fmax(0.333333333333333, 1.0 - b * b * b);
+  f->nu = 2;
+}
+static void nielsen_reject(lsqamd_fit *f) {
+  f->mu *= (double)f->nu;
+  f->nu <<= 1;
+}
+
 // ---- variable projection (nonlinear_fit's linear=, src/lsqfit/__init__.py:738-787) -------------
 // The residual is linear in the masked parameters a, and the reference hands the plugin
 // phi(theta) = min_a chi2(a, theta): its wrapped fit function solves for a at EVERY evaluation.
@@ -228,11 +276,75 @@ int legs_step(lsqamd_fit *f, Legs &L, std::vector<double> &dx) {
 // (Kaufman's form of the Golub-Pereyra Jacobian; the reference differentiates through its lstsq
 // and keeps the second term too: same minimum, slightly different iterates).  An accepted point
 // is evaluated once more at the projected a; a rejected trial restores (A, g) from a device copy.
+struct VarproStash {   // the current point's (A | g | chi2) block and host mirrors while a trial's evaluation overwrites them
+  int64_t n = 0;             // doubles of redbuf
+  bool on_device = true;     // kept in f->cov; tiny P (the tile padding exceeds P x ldm): on the host
+  std::vector<double> host, g, coln;
+  double chi2 = 0.0;
+};
+static int varpro_stash(lsqamd_fit *f, VarproStash &k) {
+  k.g = f->hg; k.coln = f->hcoln;
+  k.chi2 = f->chi2;
+  if (k.on_device) {
+    HIPCHK(f, hipMemcpyAsync(f->cov, f->redbuf, sizeof(double) * k.n, hipMemcpyDeviceToDevice, f->st));
+  } else {
+    k.host.resize(k.n);
+    HIPCHK(f, hipMemcpyAsync(k.host.data(), f->redbuf, sizeof(double) * k.n, hipMemcpyDeviceToHost, f->st));
+    HIPCHK(f, hipStreamSynchronize(f->st));
+  }
+  return 0;
+}
+static int varpro_restore(lsqamd_fit *f, const VarproStash &k) {   // back to the current point's A, g
+  if (k.on_device) HIPCHK(f, hipMemcpyAsync(f->redbuf, f->cov, sizeof(double) * k.n, hipMemcpyDeviceToDevice, f->st));
+  else {   // (on the handle's stream: the library never touches the legacy default stream -- see copy_sync in batch.hip)
+    HIPCHK(f, hipMemcpyAsync(f->redbuf, k.host.data(), sizeof(double) * k.n, hipMemcpyHostToDevice, f->st));
+    HIPCHK(f, hipStreamSynchronize(f->st));
+  }
+  f->hg = k.g; f->hcoln = k.coln;
+  f->chi2 = k.chi2;
+  f->have_dense_A = false;
+  return 0;
+}
+
+// One trial of the projected functional, from the damped step in f->hv (dt: the damping it was solved with): the current
+// point's (A, g) stashed, the full evaluation at x - v, the exact linear solve there.  -> xt, the trial point with its linear
+// parameters projected; hdx; *rho, its gain ratio (left alone when the trial point has no finite chi2 or no linear solve)
+static int varpro_trial(lsqamd_fit *f, const std::vector<double> &dt, const std::vector<double> &frozen, VarproStash &keep,
+                        std::vector<double> &xt, double *rho) {
+  const int64_t P = f->P;
+  const double chi2_cur = f->chi2;
+  double vg = 0.0, dv2 = 0.0;
+  for (int64_t j = 0; j < P; ++j) {
+    const double v = f->hv[j];
+    vg += v * f->hg[j];
+    dv2 += dt[j] * v * dt[j] * v;
+    xt[j] = f->hx[j] - v;
+  }
+  const double pred_num = vg + f->mu * dv2;      // |J v|^2 + 2 mu |D v|^2 by the system v solves
+  int rc = varpro_stash(f, keep);
+  if (rc || (rc = upload_point(f, f->p_trial, xt.data()))) return rc;
+  rc = eval_normal_dev(f, f->p_trial);           // full evaluation at the trial point ...
+  f->nfev++;
+  if (rc < 0 && rc != LSQAMD_ENONFINITE) return rc;
+  if (rc == 0) {
+    rc = solve_damped_dev(f, 0.0, nullptr, frozen.data());   // ... and the exact linear solve there
+    if (rc < 0 && rc != LSQAMD_ENOTPD) return rc;
+  }
+  if (rc != 0) return 0;
+  double chi2_t = f->chi2;
+  for (int64_t j = 0; j < P; ++j)
+    if (f->linear[j]) { chi2_t -= f->hg[j] * f->hv[j]; xt[j] -= f->hv[j]; }
+  for (int64_t j = 0; j < P; ++j) f->hdx[j] = xt[j] - f->hx[j];   // trial steps count for the xtol test
+  *rho = gain_ratio(chi2_cur, chi2_t > 0.0 ? chi2_t : 0.0, pred_num);
+  return 0;
+}
+
 int iterate_varpro(lsqamd_fit *f) {
   const int64_t P = f->P;
-  const int64_t nstash = f->npk + P + 1;
-  const bool dev_stash = P * f->ldm >= nstash;       // tiny P: the tile padding exceeds P x ldm
-  std::vector<double> host_stash, dt(P), frozen(P), xt(P), v(P), keep_g, keep_c;
+  VarproStash keep;
+  keep.n = f->npk + P + 1;
+  keep.on_device = P * f->ldm >= keep.n;
+  std::vector<double> dt(P), frozen(P), xt(P);
   for (int64_t j = 0; j < P; ++j) frozen[j] = f->linear[j] ? 0.0 : 1.0;
   int bad_steps = 0;
   while (true) {
@@ -240,78 +352,21 @@ int iterate_varpro(lsqamd_fit *f) {
     double rho = -1.0;
     int rc = solve_damped_dev(f, f->mu, dt.data());
     if (rc < 0 && rc != LSQAMD_ENOTPD) return rc;
-    bool stashed = false;
-    const double chi2_cur = f->chi2;
-    if (rc == 0) {
-      double vg = 0.0, dv2 = 0.0;
-      for (int64_t j = 0; j < P; ++j) {
-        v[j] = f->hv[j];
-        vg += v[j] * f->hg[j];
-        dv2 += dt[j] * v[j] * dt[j] * v[j];
-        xt[j] = f->hx[j] - v[j];
-      }
-      const double pred_num = vg + f->mu * dv2;      // |J v|^2 + 2 mu |D v|^2 by the system v solves
-      keep_g = f->hg; keep_c = f->hcoln;
-      if (dev_stash) {
-        HIPCHK(f, hipMemcpyAsync(f->cov, f->redbuf, sizeof(double) * nstash, hipMemcpyDeviceToDevice, f->st));
-      } else {
-        host_stash.resize(nstash);
-        HIPCHK(f, hipMemcpyAsync(host_stash.data(), f->redbuf, sizeof(double) * nstash, hipMemcpyDeviceToHost, f->st));
-        HIPCHK(f, hipStreamSynchronize(f->st));
-      }
-      stashed = true;
-      std::memcpy(f->pin_x, xt.data(), sizeof(double) * P);
-      HIPCHK(f, hipMemcpyAsync(f->p_trial, f->pin_x, sizeof(double) * P, hipMemcpyHostToDevice, f->st));
-      rc = eval_normal_dev(f, f->p_trial);           // full evaluation at the trial point ...
-      f->nfev++;
-      if (rc < 0 && rc != LSQAMD_ENONFINITE) return rc;
-      if (rc == 0) {
-        rc = solve_damped_dev(f, 0.0, nullptr, frozen.data());   // ... and the exact linear solve there
-        if (rc < 0 && rc != LSQAMD_ENOTPD) return rc;
-      }
-      if (rc == 0) {
-        double chi2_t = f->chi2;
-        for (int64_t j = 0; j < P; ++j)
-          if (f->linear[j]) { chi2_t -= f->hg[j] * f->hv[j]; xt[j] -= f->hv[j]; }
-        for (int64_t j = 0; j < P; ++j) f->hdx[j] = xt[j] - f->hx[j];   // trial steps count for the xtol test
-        const double normf = std::sqrt(chi2_cur), normf_t = std::sqrt(chi2_t > 0.0 ? chi2_t : 0.0);
-        if (normf_t < normf) {
-          const double u = normf_t / normf;
-          const double pred = pred_num / chi2_cur;
-          rho = pred > 0.0 ? (1.0 - u * u) / pred : -1.0;
-        }
-      }
-    }
+    const bool tried = rc == 0;
+    if (tried && (rc = varpro_trial(f, dt, frozen, keep, xt, &rho))) return rc;
     if (rho > 0.0) {
-      std::memcpy(f->pin_x, xt.data(), sizeof(double) * P);
-      HIPCHK(f, hipMemcpyAsync(f->p_trial, f->pin_x, sizeof(double) * P, hipMemcpyHostToDevice, f->st));
-      rc = eval_normal_dev(f, f->p_trial);           // J, A, g at the projected point
+      // the point with its linear parameters projected is not the one the trial evaluated: J, A, g there, one more nfev
+      if ((rc = upload_point(f, f->p_trial, xt.data()))) return rc;
       f->nfev++;
-      if (rc) return rc;
-      f->hx = xt;
-      std::swap(f->p_dev, f->p_trial);
-      scale_update(f);
-      const double b = 2.0 * rho - 1.0;
-      f->mu *= std::fmax(0.333333333333333, 1.0 - b * b * b);
-      f->nu = 2;
+      if ((rc = accept_trial(f, xt, true))) return rc;
+      nielsen_accept(f, rho);
       return 0;
     }
-    if (stashed) {                                   // back to the current point's A, g
-      if (dev_stash) HIPCHK(f, hipMemcpyAsync(f->redbuf, f->cov, sizeof(double) * nstash, hipMemcpyDeviceToDevice, f->st));
-      else {   // (on the handle's stream: the library never touches the legacy default stream -- see copy_sync in batch.hip)
-        HIPCHK(f, hipMemcpyAsync(f->redbuf, host_stash.data(), sizeof(double) * nstash, hipMemcpyHostToDevice, f->st));
-        HIPCHK(f, hipStreamSynchronize(f->st));
-      }
-      f->hg = keep_g; f->hcoln = keep_c;
-      f->chi2 = chi2_cur;
-      f->have_dense_A = false;
-    }
-    f->mu *= (double)f->nu;
-    f->nu <<= 1;
+    if (tried && (rc = varpro_restore(f, keep))) return rc;
+    nielsen_reject(f);
     if (++bad_steps > 15) {
-      const int rc2 = eval_normal_dev(f, f->p_dev);  // leave J, f of the CURRENT point behind
-      if (rc2) return rc2;
-      return LSQAMD_ENOPROG;
+      rc = eval_normal_dev(f, f->p_dev);  // leave J, f of the CURRENT point behind
+      return rc ? rc : LSQAMD_ENOPROG;
     }
   }
 }
@@ -485,6 +540,29 @@ static int wait_record(lsqamd_fit *f) {
   return 0;
 }
 
+// A trial with the step of the orthogonal factorisation (solver = qr, see iterate_device): the record goes back to mu0, nu0,
+// delta0, then solve, trial point, residual and decision as in enqueue_trial.  No orthogonal factor either: rejected (mu grows)
+static int qr_trial(lsqamd_fit *f, double mu0, long nu0, double delta0) {
+  const int64_t P = f->P;
+  double *rec = f->pin_lm;
+  rec[LMS_MU] = mu0; rec[LMS_NU] = (double)nu0; rec[LMS_DELTA] = delta0;
+  rec[LMS_ACCEPT] = 0.0; rec[LMS_SOLVED] = 0.0;
+  HIPCHK(f, hipMemcpyAsync(f->lmd, rec, sizeof(double) * LMS_COUNT, hipMemcpyHostToDevice, f->st));
+  int rc = solve_damped_qr(f, mu0);
+  if (rc < 0 && rc != LSQAMD_ENOTPD && rc != LSQAMD_EUNSUPPORTED) return rc;
+  if (rc != 0) {
+    f->chol_fail++;
+    rec[LMS_MU] = mu0 * (double)nu0; rec[LMS_NU] = 2.0 * (double)nu0;
+    HIPCHK(f, hipMemcpyAsync(f->lmd, rec, sizeof(double) * LMS_COUNT, hipMemcpyHostToDevice, f->st));
+    HIPCHK(f, hipStreamSynchronize(f->st));
+    return 0;
+  }
+  HIPCHK(f, launch_lm_trial(f->st, P, f->p_dev, f->yv + P, f->redbuf + f->npk, f->dscale, f->p_trial, f->lmd));
+  if ((rc = eval_residual_launch(f, f->p_trial, true)) || (rc = publish_record(f)) || (rc = wait_record(f))) return rc;
+  if (rec[LMS_SOLVED] != 0.0) f->qr_trials++;
+  return 0;
+}
+
 int iterate_device(lsqamd_fit *f) {
   const int64_t P = f->P;
   double *gvec = f->redbuf + f->npk;
@@ -515,26 +593,7 @@ int iterate_device(lsqamd_fit *f) {
     }
     f->ntrial++;
     if (need_qr) {
-      double *rec = f->pin_lm;
-      rec[LMS_MU] = mu0; rec[LMS_NU] = (double)nu0; rec[LMS_DELTA] = delta0;
-      rec[LMS_ACCEPT] = 0.0; rec[LMS_SOLVED] = 0.0;
-      HIPCHK(f, hipMemcpyAsync(f->lmd, rec, sizeof(double) * LMS_COUNT, hipMemcpyHostToDevice, f->st));
-      rc = solve_damped_qr(f, mu0);
-      if (rc < 0 && rc != LSQAMD_ENOTPD && rc != LSQAMD_EUNSUPPORTED) return rc;
-      if (rc == 0) {
-        HIPCHK(f, launch_lm_trial(f->st, P, f->p_dev, f->yv + P, gvec, f->dscale, f->p_trial, f->lmd));
-        rc = eval_residual_launch(f, f->p_trial, true);
-        if (rc) return rc;
-        if ((rc = publish_record(f))) return rc;
-        rc = wait_record(f);
-        if (rc) return rc;
-        if (st[LMS_SOLVED] != 0.0) f->qr_trials++;
-      } else {   // no orthogonal factor either: the trial is rejected (mu grows)
-        f->chol_fail++;
-        rec[LMS_MU] = mu0 * (double)nu0; rec[LMS_NU] = 2.0 * (double)nu0;
-        HIPCHK(f, hipMemcpyAsync(f->lmd, rec, sizeof(double) * LMS_COUNT, hipMemcpyHostToDevice, f->st));
-        HIPCHK(f, hipStreamSynchronize(f->st));
-      }
+      if ((rc = qr_trial(f, mu0, nu0, delta0))) return rc;
     } else if (st[LMS_SOLVED] == 0.0) {
       f->chol_fail++;
     }
@@ -567,6 +626,85 @@ int iterate_device(lsqamd_fit *f) {
   }
 }
 
+struct Proposal {   // trs->step + trs->preduction of one trial of the host-driven methods
+  std::vector<double> dx, Adx;   // the step; scratch for A dx
+  bool have_step = false;        // false: the damped matrix had no Cholesky factor -- the trial is rejected
+  double pred_num = 0.0;         // predicted reduction * chi2
+  double avratio = 0.0;          // lmaccel: |a| / |v|
+  bool residual_done = false;    // plain lm: p_trial already holds x + dx and
+  double chi2_t = 0.0;           //           chi2 there is this
+};
+
+// plain lm: everything up to the trial chi2 is queued without a host round trip -- solve, x_trial = x - v on the device,
+// residual there; one synchronisation collects v, the factorisation status and chi2(x_trial).  -> the solve's status
+static int lm_solve_and_try(lsqamd_fit *f, Proposal &s) {
+  int rc = solve_damped_launch(f, f->mu, nullptr);
+  if (rc) return rc;
+  HIPCHK(f, launch_trial_point(f->st, f->P, f->p_dev, f->yv + f->P, f->p_trial));
+  rc = eval_residual_dev(f, f->p_trial, &s.chi2_t);
+  if (rc) return rc;
+  rc = solve_damped_collect(f);
+  if (rc == LSQAMD_ENOTPD) f->nfev--;  // that residual was evaluated at garbage: not a trial
+  s.residual_done = rc == 0;
+  return rc;
+}
+
+// geodesic acceleration (lm.c lm_step, fdfvv.c) on top of the velocity in s.dx, the factor of A + mu D^2 still in place:
+// fvv by finite differences, h = 0.02; dx = v + a / 2, |a| / |v|, and lm_preduction on the corrected step
+static int lmaccel_correct(lsqamd_fit *f, Proposal &s) {
+  const int64_t P = f->P;
+  const double h = 0.02;
+  std::vector<double> vel(s.dx), xh(P), Gh(P), Av(P), rhs(P), acc(P);
+  for (int64_t j = 0; j < P; ++j) xh[j] = f->hx[j] + h * vel[j];
+  int rc = grad_like_at(f, xh.data(), Gh.data());
+  if (rc || (rc = symv_host(f, vel.data(), Av.data()))) return rc;
+  // J^T fvv = (2/h) ((G_h - g)/h - A v); the acceleration solves (A + mu D^2) a = -J^T fvv
+  for (int64_t j = 0; j < P; ++j) rhs[j] = (2.0 / h) * ((Gh[j] - f->hg[j]) / h - Av[j]);
+  rc = solve_with_factor(f, rhs.data(), acc.data());
+  if (rc) return rc;
+  double an = 0.0, vn = 0.0;
+  for (int64_t j = 0; j < P; ++j) {
+    const double a = -acc[j];
+    an += a * a;
+    vn += vel[j] * vel[j];
+    s.dx[j] = vel[j] + 0.5 * a;
+  }
+  s.avratio = std::sqrt(an) / std::sqrt(vn);
+  // lm_preduction on dx: |J dx|^2 + 2 mu |D dx|^2
+  rc = symv_host(f, s.dx.data(), s.Adx.data());
+  if (rc) return rc;
+  const double dn = scaled_norm(f->hdiag, s.dx);
+  s.pred_num = dot_h(s.dx, s.Adx) + 2.0 * f->mu * dn * dn;
+  return 0;
+}
+
+// lm / lmaccel: the damped solve, dx = -v and its predicted reduction
+static int propose_lm(lsqamd_fit *f, Proposal &s) {
+  const int rc = f->opt.trs == LSQAMD_TRS_LM ? lm_solve_and_try(f, s) : solve_damped_dev(f, f->mu, f->hdiag.data());
+  if (rc < 0 && rc != LSQAMD_ENOTPD) return rc;
+  if (rc != 0) return 0;
+  s.have_step = true;
+  double vg = 0.0, dv2 = 0.0;
+  for (int64_t j = 0; j < f->P; ++j) {
+    s.dx[j] = -f->hv[j];
+    vg += f->hv[j] * f->hg[j];
+    const double t = f->hdiag[j] * f->hv[j];
+    dv2 += t * t;
+  }
+  // |J v|^2 = v^T A v = v^T g - mu |D v|^2  since (A + mu D^2) v = g
+  s.pred_num = vg + f->mu * dv2;
+  return f->opt.trs == LSQAMD_TRS_LMACCEL ? lmaccel_correct(f, s) : 0;
+}
+
+// dogleg, ddogleg, subspace2D: the step for the current radius and quadratic_preduction, -(|J dx|^2 + 2 g.dx)
+static int propose_legs(lsqamd_fit *f, Legs &L, Proposal &s) {
+  int rc = legs_step(f, L, s.dx);
+  if (rc || (rc = symv_host(f, s.dx.data(), s.Adx.data()))) return rc;
+  s.have_step = true;
+  s.pred_num = -(dot_h(s.dx, s.Adx) + 2.0 * dot_h(f->hg, s.dx));
+  return 0;
+}
+
 // one trust_iterate: GSL_SUCCESS (0) or LSQAMD_ENOPROG; negative on backend failure
 int iterate(lsqamd_fit *f) {
   if (f->dev_lm && f->opt.trs == LSQAMD_TRS_LM && f->linear.empty()) return iterate_device(f);
@@ -580,120 +718,37 @@ int iterate(lsqamd_fit *f) {
   const int trs = f->opt.trs;
   const bool lm_family = trs == LSQAMD_TRS_LM || trs == LSQAMD_TRS_LMACCEL;
   int bad_steps = 0;
-  std::vector<double> xt(P), dx(P), tmp(P);
+  std::vector<double> xt(P);
+  Proposal s;
+  s.dx.resize(P); s.Adx.resize(P);
   Legs L;
   if (!lm_family) {
     const int rc = legs_preloop(f, L);
     if (rc) return rc;
   }
   while (true) {
-    double rho = -1.0, avratio = 0.0;
-    bool have_step = false;
-    double pred_num = 0.0;  // predicted reduction * chi2
-    bool residual_done = false;
-    double chi2_fast = 0.0;
-    if (lm_family) {
-      int rc;
-      if (trs == LSQAMD_TRS_LM) {
-        // plain lm: everything up to the trial chi2 is queued without a host round trip --
-        // solve, x_trial = x - v on the device, residual there; one synchronisation collects
-        // v, the factorisation status and chi2(x_trial)
-        rc = solve_damped_launch(f, f->mu, nullptr);
-        if (rc) return rc;
-        HIPCHK(f, launch_trial_point(f->st, P, f->p_dev, f->yv + P, f->p_trial));
-        rc = eval_residual_dev(f, f->p_trial, &chi2_fast);
-        if (rc) return rc;
-        rc = solve_damped_collect(f);
-        if (rc == LSQAMD_ENOTPD) f->nfev--;  // that residual was evaluated at garbage: not a trial
-        residual_done = rc == 0;
-      } else {
-        rc = solve_damped_dev(f, f->mu, f->hdiag.data());
-      }
-      if (rc < 0 && rc != LSQAMD_ENOTPD) return rc;
-      if (rc == 0) {
-        have_step = true;
-        double vg = 0.0, dv2 = 0.0;
-        for (int64_t j = 0; j < P; ++j) {
-          dx[j] = -f->hv[j];
-          vg += f->hv[j] * f->hg[j];
-          const double t = f->hdiag[j] * f->hv[j];
-          dv2 += t * t;
-        }
-        // |J v|^2 = v^T A v = v^T g - mu |D v|^2  since (A + mu D^2) v = g
-        pred_num = vg + f->mu * dv2;
-        if (trs == LSQAMD_TRS_LMACCEL) {
-          // geodesic acceleration (lm.c lm_step, fdfvv.c): fvv by finite differences, h = 0.02
-          const double h = 0.02;
-          std::vector<double> vel(dx), xh(P), Gh(P), Av(P), rhs(P), acc(P);
-          for (int64_t j = 0; j < P; ++j) xh[j] = f->hx[j] + h * vel[j];
-          rc = grad_like_at(f, xh.data(), Gh.data());
-          if (rc) return rc;
-          rc = symv_host(f, vel.data(), Av.data());
-          if (rc) return rc;
-          // J^T fvv = (2/h) ((G_h - g)/h - A v); the acceleration solves (A + mu D^2) a = -J^T fvv
-          for (int64_t j = 0; j < P; ++j) rhs[j] = (2.0 / h) * ((Gh[j] - f->hg[j]) / h - Av[j]);
-          rc = solve_with_factor(f, rhs.data(), acc.data());
-          if (rc) return rc;
-          double an = 0.0, vn = 0.0;
-          for (int64_t j = 0; j < P; ++j) {
-            const double a = -acc[j];
-            an += a * a;
-            vn += vel[j] * vel[j];
-            dx[j] = vel[j] + 0.5 * a;
-          }
-          avratio = std::sqrt(an) / std::sqrt(vn);
-          // lm_preduction on dx: |J dx|^2 + 2 mu |D dx|^2
-          rc = symv_host(f, dx.data(), tmp.data());
-          if (rc) return rc;
-          const double dn = scaled_norm(f->hdiag, dx);
-          pred_num = dot_h(dx, tmp) + 2.0 * f->mu * dn * dn;
-        }
-      }
-    } else {
-      const int rc = legs_step(f, L, dx);
-      if (rc) return rc;
-      have_step = true;
-      // quadratic_preduction: -(|J dx|^2 + 2 g.dx)
-      const int rc2 = symv_host(f, dx.data(), tmp.data());
-      if (rc2) return rc2;
-      pred_num = -(dot_h(dx, tmp) + 2.0 * dot_h(f->hg, dx));
-    }
-    if (have_step) {
+    s.have_step = s.residual_done = false;
+    s.pred_num = s.avratio = s.chi2_t = 0.0;
+    int rc = lm_family ? propose_lm(f, s) : propose_legs(f, L, s);
+    if (rc) return rc;
+    double rho = -1.0;
+    if (s.have_step) {
       for (int64_t j = 0; j < P; ++j) {
-        f->hdx[j] = dx[j];
-        xt[j] = f->hx[j] + dx[j];
+        f->hdx[j] = s.dx[j];
+        xt[j] = f->hx[j] + s.dx[j];
       }
-      double chi2_t = chi2_fast;
-      if (!residual_done) {
-        std::memcpy(f->pin_x, xt.data(), sizeof(double) * P);
-        HIPCHK(f, hipMemcpyAsync(f->p_trial, f->pin_x, sizeof(double) * P, hipMemcpyHostToDevice, f->st));
-        const int rc = eval_residual_dev(f, f->p_trial, &chi2_t);
-        if (rc) return rc;
-      }
-      const double normf = std::sqrt(f->chi2), normf_t = std::sqrt(chi2_t);
-      if (normf_t < normf) {  // NaN-safe: anything else rejects
-        const double u = normf_t / normf;
-        const double actual = 1.0 - u * u;
-        const double pred = pred_num / f->chi2;
-        rho = pred > 0.0 ? actual / pred : -1.0;
-      }
+      if (!s.residual_done && (rc = trial_residual(f, xt.data(), &s.chi2_t))) return rc;
+      rho = gain_ratio(f->chi2, s.chi2_t, s.pred_num);
     }
     if (rho > 0.75) f->delta *= f->opt.factor_up;
     else if (rho < 0.25) f->delta /= f->opt.factor_down;
     // trust_eval_step: with geodesic acceleration the step must also satisfy |a|/|v| <= avmax
-    if (rho > 0.0 && !(trs == LSQAMD_TRS_LMACCEL && avratio > f->opt.avmax)) {
-      const int rc = eval_normal_dev(f, f->p_trial);
-      if (rc) return rc;
-      f->hx = xt;
-      std::swap(f->p_dev, f->p_trial);
-      scale_update(f);
-      const double b = 2.0 * rho - 1.0;
-      f->mu *= std::fmax(0.333333333333333, 1.0 - b * b * b);
-      f->nu = 2;
+    if (rho > 0.0 && !(trs == LSQAMD_TRS_LMACCEL && s.avratio > f->opt.avmax)) {
+      if ((rc = accept_trial(f, xt, true))) return rc;
+      nielsen_accept(f, rho);
       return 0;
     }
-    f->mu *= (double)f->nu;
-    f->nu <<= 1;
+    nielsen_reject(f);
     if (++bad_steps > 15) return LSQAMD_ENOPROG;
   }
 }
@@ -712,6 +767,41 @@ int convergence_test(lsqamd_fit *f) {
     if (t > gnorm) gnorm = t;
   }
   if (gnorm <= gtol * std::fmax(0.5 * f->chi2, 1.0)) return 2;
+  return 0;
+}
+
+// nonlinear_fit's linear= (lsqamd_set_linear): variable projection (iterate_varpro) starts from the projected point --
+// A_aa da = -g_a with the others frozen, one more evaluation
+static int varpro_start(lsqamd_fit *f) {
+  const int64_t P = f->P;
+  std::vector<double> frozen(P);
+  for (int64_t j = 0; j < P; ++j) frozen[j] = f->linear[j] ? 0.0 : 1.0;
+  int rc = solve_damped_dev(f, 0.0, nullptr, frozen.data());
+  if (rc == LSQAMD_ENOTPD) FAIL(f, LSQAMD_ENOTPD, "linear parameters: their block of J^T J is not positive definite");
+  if (rc) return rc;
+  for (int64_t j = 0; j < P; ++j)
+    if (f->linear[j]) f->hx[j] -= f->hv[j];
+  if ((rc = upload_point(f, f->p_dev, f->hx.data())) || (rc = eval_normal_dev(f, f->p_dev))) return rc;
+  f->nfev++;
+  return 0;
+}
+
+// plain lm on the device: the record its decisions start from (once per fit), from the handle's chi2, mu, nu, delta
+static int start_device_record(lsqamd_fit *f) {
+  for (int i = 0; i < LMS_COUNT; ++i) f->pin_lm[i] = 0.0;
+  f->pin_lm[LMS_CHI2] = f->chi2; f->pin_lm[LMS_MU] = f->mu; f->pin_lm[LMS_NU] = (double)f->nu;
+  f->pin_lm[LMS_DELTA] = f->delta;
+  // the kernels that finish a half step mirror the record into this pinned block themselves (LSQAMD_ZERO_COPY=0: a copy per read)
+  const char *zc = getenv("LSQAMD_ZERO_COPY");      // (read per call: a tested mode)
+  const bool off = zc && zc[0] == '0';
+  void *dp = nullptr;
+  f->lm_zero_copy = !off && hipHostGetDevicePointer(&dp, f->pin_lm, 0) == hipSuccess && dp != nullptr;
+  if (!f->lm_zero_copy) (void)hipGetLastError();
+  long long bits = f->lm_zero_copy ? (long long)(intptr_t)dp : 0;
+  std::memcpy(&f->pin_lm[LMS_HOSTPTR], &bits, sizeof(double));
+  f->lm_seq_expect = 0.0;
+  HIPCHK(f, hipMemcpyAsync(f->lmd, f->pin_lm, sizeof(double) * LMS_COUNT, hipMemcpyHostToDevice, f->st));
+  HIPCHK(f, hipStreamSynchronize(f->st));
   return 0;
 }
 
@@ -734,22 +824,7 @@ int do_init(lsqamd_fit *f, const double *p0) {
   rc = eval_normal_dev(f, f->p_dev);
   if (rc) return rc;
   f->nfev++;
-  if (!f->linear.empty()) {
-    // nonlinear_fit's linear= (lsqamd_set_linear): variable projection (iterate_varpro) starts from
-    // the projected point -- A_aa da = -g_a with the others frozen, one more evaluation
-    std::vector<double> frozen(P);
-    for (int64_t j = 0; j < P; ++j) frozen[j] = f->linear[j] ? 0.0 : 1.0;
-    rc = solve_damped_dev(f, 0.0, nullptr, frozen.data());
-    if (rc == LSQAMD_ENOTPD) FAIL(f, LSQAMD_ENOTPD, "linear parameters: their block of J^T J is not positive definite");
-    if (rc) return rc;
-    for (int64_t j = 0; j < P; ++j)
-      if (f->linear[j]) f->hx[j] -= f->hv[j];
-    std::memcpy(f->pin_x, f->hx.data(), sizeof(double) * P);
-    HIPCHK(f, hipMemcpyAsync(f->p_dev, f->pin_x, sizeof(double) * P, hipMemcpyHostToDevice, f->st));
-    rc = eval_normal_dev(f, f->p_dev);
-    if (rc) return rc;
-    f->nfev++;
-  }
+  if (!f->linear.empty() && (rc = varpro_start(f))) return rc;
   scale_init(f);
   double mx = 0.0;   // over the damped parameters (all of them unless lsqamd_set_linear was used)
   for (int64_t j = 0; j < P; ++j)
@@ -762,24 +837,45 @@ int do_init(lsqamd_fit *f, const double *p0) {
   f->mirrors_stale = false;
   f->conv_info_dev = 0;
   f->dev_lm = f->opt.trs == LSQAMD_TRS_LM && f->linear.empty() && getenv("LSQAMD_HOST_LM") == nullptr;
-  if (f->dev_lm) {   // the record the device-side decisions start from (once per fit)
-    for (int i = 0; i < LMS_COUNT; ++i) f->pin_lm[i] = 0.0;
-    f->pin_lm[LMS_CHI2] = f->chi2; f->pin_lm[LMS_MU] = f->mu; f->pin_lm[LMS_NU] = (double)f->nu;
-    f->pin_lm[LMS_DELTA] = f->delta;
-    {   // the kernels that finish a half step mirror the record into this pinned block themselves (LSQAMD_ZERO_COPY=0: a copy per read)
-      const char *zc = getenv("LSQAMD_ZERO_COPY");      // (read per call: a tested mode)
-      const bool off = zc && zc[0] == '0';
-      void *dp = nullptr;
-      f->lm_zero_copy = !off && hipHostGetDevicePointer(&dp, f->pin_lm, 0) == hipSuccess && dp != nullptr;
-      if (!f->lm_zero_copy) (void)hipGetLastError();
-      long long bits = f->lm_zero_copy ? (long long)(intptr_t)dp : 0;
-      std::memcpy(&f->pin_lm[LMS_HOSTPTR], &bits, sizeof(double));
-      f->lm_seq_expect = 0.0;
-    }
-    HIPCHK(f, hipMemcpyAsync(f->lmd, f->pin_lm, sizeof(double) * LMS_COUNT, hipMemcpyHostToDevice, f->st));
-    HIPCHK(f, hipStreamSynchronize(f->st));
-  }
+  if (f->dev_lm && (rc = start_device_record(f))) return rc;
   f->initialised = true;
+  return 0;
+}
+
+// One pass of gsl_multifit_nlinear_driver's loop: trust_iterate, nit, the convergence test -> 0 with *info the criterion
+// met (0: none).  An iteration without progress is tested like any other unless stall_ends: then LSQAMD_ENOPROG, *info too
+int driver_iteration(lsqamd_fit *f, int *info, bool stall_ends) {
+  const int rc = iterate(f);
+  if (rc < 0) return rc;
+  f->nit++;
+  if (rc == LSQAMD_ENOPROG && stall_ends) {
+    *info = LSQAMD_ENOPROG;
+    return LSQAMD_ENOPROG;
+  }
+  *info = convergence_test(f);
+  return 0;
+}
+
+// gsl_multifit_nlinear_init + _driver (src/lsqfit/_gsl.pyx:676-677) from p0.  *info as driver_iteration leaves it (0 without
+// an iteration); *status 0: converged, or maxit < 1; LSQAMD_EMAXITER: out of iterations, or the first one made no progress
+int run_gsl_driver(lsqamd_fit *f, const double *p0, int *status, int *info) {
+  int rc = do_init(f, p0);
+  if (rc) return rc;
+  const int maxit = f->opt.maxit;
+  *status = 0;
+  if (maxit <= 0) return 0;
+  int iter = 0;
+  do {
+    rc = driver_iteration(f, info, iter == 0);
+    if (rc < 0) return rc;
+    if (rc == LSQAMD_ENOPROG) {
+      *status = LSQAMD_EMAXITER;
+      return 0;
+    }
+    ++iter;
+    *status = *info ? 0 : -2;
+  } while (*status == -2 && iter < maxit);
+  if (iter >= maxit && *status != 0) *status = LSQAMD_EMAXITER;
   return 0;
 }
 
@@ -810,48 +906,38 @@ void fill_summary(lsqamd_fit *f, lsqamd_summary *s, int status, int info) {
 // half dozen launches and two host round trips of an iteration of iterate_device cost more than its arithmetic.  One workgroup
 // runs gsl_multifit_nlinear_init + _driver (src/lsqfit/_gsl.pyx:676-677) from p0 to the stopping criterion -- and, for the
 // normal-equation route, gsl_multifit_nlinear_covar (:706) -- and hands back the state where do_init / iterate_device
-// would have left it (device buffers and host mirrors).  -> 1: done (iter, info set); 0: not this fit's route, or the kernel met
-// something irregular and the general path runs the fit from the start; < 0: error.  LSQAMD_ONE_LAUNCH_FIT=0 disables (read per call).
-int run_one_launch(lsqamd_fit *f, const double *p0, int *iter, int *info) {
+// would have left it (device buffers and host mirrors).  Here in stages: who takes the route, the kernel's arguments, the wait
+// for its record block, the block's audit, its adoption into the handle; run_one_launch at the end.
+using namespace lsqamd_jit;   // (the record block's layout: FIT_REC_*, fit_host_diag, fit_host_cov)
+
+struct FitLaunch {   // one launch of the fit kernel
+  void *dfit = nullptr, *dx = nullptr, *dlm = nullptr;   // the device's addresses of pin_fit, pin_x, pin_lm
+  bool zero_copy = true;                                 // the kernel publishes its record block to pin_fit
+  unsigned long long seq = 0;                            // how the host tells this launch's block from an earlier one's
+  int nw = 0;                                            // words of the record block of a P-parameter fit
+};
+
+static bool one_launch_eligible(const lsqamd_fit *f) {
   const char *e = getenv("LSQAMD_ONE_LAUNCH_FIT");
-  if (e && e[0] == '0') return 0;
-  const int64_t P = f->P;
-  const lsqamd_jit::Kernel *k = static_cast<const lsqamd_jit::Kernel *>(f->jit);
-  if (!lsqamd_jit::has_fit_kernel(k) || P > lsqamd_jit::FIT_MAX_P || f->N < 1 ||
-      f->N > lsqamd_jit::fit_row_limit(k, f->cfg.n_blocks != 0)) return 0;
-  if (f->opt.trs != LSQAMD_TRS_LM || !f->linear.empty() || getenv("LSQAMD_HOST_LM") || f->opt.maxit < 1) return 0;
-  if (f->opt.maxit > 20000) return 0;      // (a kernel cannot be interrupted: runs of that length stay on the host-driven path)
-  if (f->comm || f->reduce || f->timing || !small_fuse(f) || !f->progs.empty() || f->have_param_rows) return 0;
+  if (e && e[0] == '0') return false;
+  const Kernel *k = static_cast<const Kernel *>(f->jit);
+  if (!has_fit_kernel(k) || f->P > FIT_MAX_P || f->N < 1 || f->N > fit_row_limit(k, f->cfg.n_blocks != 0)) return false;
+  if (f->opt.trs != LSQAMD_TRS_LM || !f->linear.empty() || getenv("LSQAMD_HOST_LM") || f->opt.maxit < 1) return false;
+  if (f->opt.maxit > 20000) return false;  // (a kernel cannot be interrupted: runs of that length stay on the host-driven path)
+  if (f->comm || f->reduce || f->timing || !small_fuse(f) || !f->progs.empty() || f->have_param_rows) return false;
   // correlated rows: the workgroup whitens them itself (one row per thread, the raw rows in LDS) -- up to 256 rows in all
-  if (f->cfg.n_blocks > 64) return 0;
-  if (f->cfg.has_prior && !f->adds_prior) return 0;
-  int rc = ready(f);
-  if (rc) return rc;
-  void *dfit = nullptr, *dx = nullptr, *dlm = nullptr;
-  if (!f->fit_block || hipHostGetDevicePointer(&dfit, f->pin_fit, 0) != hipSuccess || hipHostGetDevicePointer(&dx, f->pin_x, 0) != hipSuccess ||
-      hipHostGetDevicePointer(&dlm, f->pin_lm, 0) != hipSuccess || !dfit || !dx || !dlm) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  // LSQAMD_ZERO_COPY=0 (read per call: a tested mode): nothing is published to host memory; the host waits for the stream and
-  // copies the kernel's device block -- also what happens when a published block does not verify in time
-  const char *z = getenv("LSQAMD_ZERO_COPY");
-  const bool zc_off = z && z[0] == '0';
-  const int nw = lsqamd_jit::fit_host_cov((int)P) + (int)(P * P);       // words of the record block of a P-parameter fit
-  static std::atomic<unsigned> g_seq{0};
-  unsigned long long seq = 0;
-  while (seq == 0) seq = (g_seq.fetch_add(1, std::memory_order_relaxed) + 1u) & 0xffffffu;   // 24 bits, never 0
-  std::memcpy(f->pin_x, p0, sizeof(double) * P);
-  volatile unsigned long long *hw = reinterpret_cast<volatile unsigned long long *>(f->pin_fit);
-  if (poison_pinned()) poison_fill(f->pin_fit, sizeof(double) * lsqamd_jit::FIT_HOST_DOUBLES);
-  hw[16] = 0;
-  std::atomic_thread_fence(std::memory_order_release);
-  lsqamd_jit::FitArgs a;
+  if (f->cfg.n_blocks > 64) return false;
+  return !(f->cfg.has_prior && !f->adds_prior);
+}
+
+static FitArgs fit_args(const lsqamd_fit *f, const FitLaunch &L) {
+  const int64_t P = f->P;
+  FitArgs a;
   a.x = f->x; a.ymean = f->ymean; a.wdiag = f->wdiag; a.n_data = f->N;
   a.in_block = f->in_block; a.wt = f->wt;
   a.blk_row0 = reinterpret_cast<const long long *>(f->blk_row0); a.blk_size = reinterpret_cast<const long long *>(f->blk_size);
   a.blk_woff = reinterpret_cast<const long long *>(f->blk_woff); a.n_blocks = f->cfg.n_blocks;
-  a.p0 = static_cast<const double *>(dx);
+  a.p0 = static_cast<const double *>(L.dx);
   a.p = f->p_dev; a.p_trial = f->p_trial; a.dscale = f->dscale; a.apk = f->redbuf; a.gvec = f->redbuf + f->npk;
   a.v_out = f->yv + P; a.coln2 = f->diag_dev; a.st = f->lmd;
   a.prior_prec = f->cfg.has_prior ? f->prior_prec : nullptr;
@@ -859,35 +945,44 @@ int run_one_launch(lsqamd_fit *f, const double *p0, int *iter, int *info) {
   a.prior_dense = f->cfg.prior_dense; a.scaler = f->opt.scaler; a.maxit = f->opt.maxit;
   a.watch = f->opt.solver == LSQAMD_SOLVER_QR ? 1 : 0;
   a.xtol = f->opt.xtol; a.gtol = f->opt.gtol; a.factor_up = f->opt.factor_up; a.factor_down = f->opt.factor_down;
-  const long long bits = zc_off ? 0 : (long long)(intptr_t)dlm;
+  // LSQAMD_ZERO_COPY=0: nothing is published to host memory; the host waits for the stream and copies the kernel's device
+  // block -- also what happens when a published block does not verify in time
+  const long long bits = L.zero_copy ? (long long)(intptr_t)L.dlm : 0;
   std::memcpy(&a.hostptr_bits, &bits, sizeof(double));
   a.host = f->fit_block;
-  a.pub = zc_off ? nullptr : static_cast<unsigned long long *>(dfit);
-  a.seq = seq;
+  a.pub = L.zero_copy ? static_cast<unsigned long long *>(L.dfit) : nullptr;
+  a.seq = L.seq;
   // the covariance of the normal-equation route rides along (solver = qr factors the Jacobian itself: do_covariance_qr)
   a.cov = f->cov; a.ldc = f->ldm; a.want_cov = f->opt.solver == LSQAMD_SOLVER_QR ? 0 : 1; a.pad_ = 0;
-  HIPCHK(f, lsqamd_jit::launch_fit(k, f->st, a));
+  return a;
+}
+
+// The launch's record block -> f->fit_rec.  A published block (zero copy) is polled for: the flag word is this launch's only when
+// it carries this launch's sequence number; the block behind it counts only when its checksum (seeded with the same number)
+// fits the snapshot taken -- the kernel's stores arrive in no particular order (jit.hip, end of lm_fit).  A short spin (most
+// small fits end within 100 us), then yielding the core, then the stream; a block that still does not verify once the
+// stream has drained, like one that was never published, is the device's copy.
+static int await_fit_record(lsqamd_fit *f, const FitLaunch &L) {
+  const int nw = L.nw;
+  const unsigned long long seq = L.seq;
   f->fit_rec.resize((size_t)nw);
+  volatile unsigned long long *hw = reinterpret_cast<volatile unsigned long long *>(f->pin_fit);
   unsigned long long *rec = reinterpret_cast<unsigned long long *>(f->fit_rec.data());
+  auto arrived = [&]() {
+    const unsigned long long flag = hw[FIT_REC_REASON];
+    if ((flag >> 40) != seq) return false;
+    std::atomic_thread_fence(std::memory_order_acquire);
+    for (int i = 0; i < nw; ++i) rec[i] = hw[i];
+    if (rec[FIT_REC_REASON] != flag || rec[FIT_REC_CHECK] != fit_checksum(rec, nw, seq)) { g_handoff[0]++; return false; }
+    // the flag IS the decision: reason | info | nit; the record behind it must say the same
+    const int reason = (int)(flag & 0xff), info = (int)(int8_t)((flag >> 8) & 0xff), nit = (int)((flag >> 16) & 0xffffff);
+    if ((int)f->fit_rec[LMS_INFO] != info || (int)f->fit_rec[FIT_REC_NIT] != nit) { g_handoff[0]++; return false; }
+    f->fit_rec[FIT_REC_REASON] = (double)reason;
+    f->fit_rec[FIT_REC_CHECK] = 0.0;
+    return true;
+  };
   bool have = false;
-  if (a.pub) {
-    // The flag word is this launch's only when it carries this launch's sequence number; the block behind it counts only when
-    // its checksum (seeded with the same number) fits the snapshot taken -- the kernel's stores arrive in no particular
-    // order (jit.hip, end of lm_fit).  A short spin (most small fits end within 100 us), then yielding the core, then the
-    // stream; a block that still does not verify once the stream has drained is replaced by the device copy.
-    auto arrived = [&]() {
-      const unsigned long long flag = hw[16];
-      if ((flag >> 40) != seq) return false;
-      std::atomic_thread_fence(std::memory_order_acquire);
-      for (int i = 0; i < nw; ++i) rec[i] = hw[i];
-      if (rec[16] != flag || rec[23] != lsqamd_jit::fit_checksum(rec, nw, seq)) { g_handoff[0]++; return false; }
-      // the flag IS the decision: reason | info | nit; the record behind it must say the same
-      const int reason = (int)(flag & 0xff), info = (int)(int8_t)((flag >> 8) & 0xff), nit = (int)((flag >> 16) & 0xffffff);
-      if ((int)f->fit_rec[LMS_INFO] != info || (int)f->fit_rec[17] != nit) { g_handoff[0]++; return false; }
-      f->fit_rec[16] = (double)reason;
-      f->fit_rec[23] = 0.0;
-      return true;
-    };
+  if (L.zero_copy) {
     have = poll(arrived, 5000);
     if (!have) {
       HIPCHK(f, hipStreamSynchronize(f->st));
@@ -900,25 +995,34 @@ int run_one_launch(lsqamd_fit *f, const double *p0, int *iter, int *info) {
     HIPCHK(f, hipMemcpyAsync(f->fit_rec.data(), f->fit_block, sizeof(double) * (size_t)nw, hipMemcpyDeviceToHost, f->st));
     HIPCHK(f, hipStreamSynchronize(f->st));
   }
-  if (getenv("LSQAMD_VERIFY_HANDOFF")) {   // test knob: the block the host acted on vs the device's own copy once the stream has drained
-    std::vector<double> dev((size_t)nw);
-    HIPCHK(f, hipStreamSynchronize(f->st));
-    HIPCHK(f, hipMemcpyAsync(dev.data(), f->fit_block, sizeof(double) * (size_t)nw, hipMemcpyDeviceToHost, f->st));
-    HIPCHK(f, hipStreamSynchronize(f->st));
-    int bad = 0;
-    for (int i = 0; i < nw; ++i)
-      if (i != 23 && std::memcmp(&dev[(size_t)i], &f->fit_rec[(size_t)i], sizeof(double)) != 0) {
-        fprintf(stderr, "lsqamd HANDOFF MISMATCH word %d: host %a device %a\n", i, f->fit_rec[(size_t)i], dev[(size_t)i]);
-        ++bad;
-      }
-    if (bad) { g_handoff[2] += bad; fprintf(stderr, "lsqamd HANDOFF: %d mismatches (P %lld N %lld)\n", bad, (long long)P, (long long)f->N); }
+  return 0;
+}
+
+// LSQAMD_VERIFY_HANDOFF (test knob): the block the host acted on vs the device's own copy once the stream has drained
+static int audit_fit_record(lsqamd_fit *f, int nw) {
+  std::vector<double> dev((size_t)nw);
+  HIPCHK(f, hipStreamSynchronize(f->st));
+  HIPCHK(f, hipMemcpyAsync(dev.data(), f->fit_block, sizeof(double) * (size_t)nw, hipMemcpyDeviceToHost, f->st));
+  HIPCHK(f, hipStreamSynchronize(f->st));
+  int bad = 0;
+  for (int i = 0; i < nw; ++i)
+    if (i != FIT_REC_CHECK && std::memcmp(&dev[(size_t)i], &f->fit_rec[(size_t)i], sizeof(double)) != 0) {
+      fprintf(stderr, "lsqamd HANDOFF MISMATCH word %d: host %a device %a\n", i, f->fit_rec[(size_t)i], dev[(size_t)i]);
+      ++bad;
+    }
+  if (bad) {
+    g_handoff[2] += bad;
+    fprintf(stderr, "lsqamd HANDOFF: %d mismatches (P %lld N %lld)\n", bad, (long long)f->P, (long long)f->N);
   }
+  return 0;
+}
+
+// A finished fit's record block (f->fit_rec) into the handle: the host mirrors, the LM record, the counters, the flags as
+// do_init / iterate_device would have left them, the covariance's state
+static void adopt_fit_record(lsqamd_fit *f, bool zero_copy, bool want_cov) {
+  const int64_t P = f->P;
   const double *R = f->fit_rec.data();
-  if (R[16] != 1.0) {                 // irregular: the general path from the start
-    HIPCHK(f, hipStreamSynchronize(f->st));
-    return 0;
-  }
-  const double *m = R + 24;
+  const double *m = R + FIT_REC_MIRRORS;
   f->hx.assign(m, m + P);
   f->hg.assign(m + (P + 1), m + (P + 1) + P);
   f->hdiag.assign(m + 2 * (P + 1), m + 2 * (P + 1) + P);
@@ -930,39 +1034,74 @@ int run_one_launch(lsqamd_fit *f, const double *p0, int *iter, int *info) {
     f->hdx[j] = -v;
   }
   for (int i = 0; i < LMS_COUNT; ++i) f->pin_lm[i] = R[i];
-  f->nit = (int)R[17]; f->nfev = (int)R[18]; f->njev = (int)R[19]; f->ntrial = (int)R[20];
+  f->nit = (int)R[FIT_REC_NIT]; f->nfev = (int)R[FIT_REC_NFEV]; f->njev = (int)R[FIT_REC_NJEV]; f->ntrial = (int)R[FIT_REC_NTRIAL];
   f->chol_fail = f->qr_trials = 0;
   f->qr_steps_on = false;
   f->logdet = NAN;
   f->chi2 = R[LMS_CHI2]; f->mu = R[LMS_MU]; f->nu = (long)R[LMS_NU]; f->delta = R[LMS_DELTA];
   f->conv_info_dev = (int32_t)R[LMS_INFO];
   f->dev_lm = true;
-  f->lm_zero_copy = bits != 0;
+  f->lm_zero_copy = zero_copy;
   f->lm_seq_expect = 0.0;
   f->mirrors_stale = false;
   f->J_stale = true;               // (no Jacobian was written: ensure_J() for whoever reads it)
   f->used_nrm = true;
   f->used_one_launch = true;
-  if (getenv("LSQAMD_FIT_DIAG"))     // developer knob: where the kernel's cycles went
+  if (getenv("LSQAMD_FIT_DIAG")) {   // developer knob: where the kernel's cycles went
+    const double *c = R + fit_host_diag((int)P);
     fprintf(stderr, "lsqamd_jit_lm: %.0f shader cycles (normal equations %.0f, solves %.0f, trial residuals %.0f), %.1f us; nit %d trials %d\n",
-            R[lsqamd_jit::fit_host_diag((int)P)], R[lsqamd_jit::fit_host_diag((int)P) + 1], R[lsqamd_jit::fit_host_diag((int)P) + 2],
-            R[lsqamd_jit::fit_host_diag((int)P) + 3], R[lsqamd_jit::fit_host_diag((int)P) + 4] / 100.0, (int)f->nit, (int)f->ntrial);
+            c[0], c[1], c[2], c[3], c[4] / 100.0, (int)f->nit, (int)f->ntrial);
+  }
   f->nrm_in_tail = 0;
   f->prior_deferred = false;
   f->r_fresh = false;
   f->have_cov = false;
   f->cov_host_valid = false;
-  if (a.want_cov && R[21] == 1.0) {     // (else: do_covariance, the caller's next step)
+  if (want_cov && R[FIT_REC_HAVE_COV] == 1.0) {     // (else: do_covariance, the caller's next step)
     f->have_cov = true;
     f->cov_host_valid = true;
     f->cov_inaccurate = false;
     f->cov_dropped = 0;
-    f->logdet = R[22];
+    f->logdet = R[FIT_REC_LOGDET];
   }
   f->have_dense_A = false;
   f->initialised = true;
-  *iter = (int)f->nit;
+}
+
+// -> 1: done (*info: the criterion met, 0 none; *status: 0, -2 or LSQAMD_EMAXITER as the driver loop would have left it); 0: not
+// this fit's route, or the kernel met something irregular and the general path runs the fit from the start; < 0: error.
+// LSQAMD_ONE_LAUNCH_FIT=0 disables, LSQAMD_ZERO_COPY=0 keeps the record block off host memory (both read per call: tested modes)
+int run_one_launch(lsqamd_fit *f, const double *p0, int *status, int *info) {
+  if (!one_launch_eligible(f)) return 0;
+  int rc = ready(f);
+  if (rc) return rc;
+  FitLaunch L;
+  if (!f->fit_block || hipHostGetDevicePointer(&L.dfit, f->pin_fit, 0) != hipSuccess || hipHostGetDevicePointer(&L.dx, f->pin_x, 0) != hipSuccess ||
+      hipHostGetDevicePointer(&L.dlm, f->pin_lm, 0) != hipSuccess || !L.dfit || !L.dx || !L.dlm) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  const char *z = getenv("LSQAMD_ZERO_COPY");
+  L.zero_copy = !(z && z[0] == '0');
+  L.nw = fit_host_cov((int)f->P) + (int)(f->P * f->P);
+  static std::atomic<unsigned> g_seq{0};
+  while (L.seq == 0) L.seq = (g_seq.fetch_add(1, std::memory_order_relaxed) + 1u) & 0xffffffu;   // 24 bits, never 0
+  std::memcpy(f->pin_x, p0, sizeof(double) * f->P);
+  if (poison_pinned()) poison_fill(f->pin_fit, sizeof(double) * FIT_HOST_DOUBLES);
+  reinterpret_cast<volatile unsigned long long *>(f->pin_fit)[FIT_REC_REASON] = 0;   // no flag yet
+  std::atomic_thread_fence(std::memory_order_release);
+  const Kernel *k = static_cast<const Kernel *>(f->jit);
+  const FitArgs a = fit_args(f, L);
+  HIPCHK(f, lsqamd_jit::launch_fit(k, f->st, a));
+  if ((rc = await_fit_record(f, L))) return rc;
+  if (getenv("LSQAMD_VERIFY_HANDOFF") && (rc = audit_fit_record(f, L.nw))) return rc;
+  if (f->fit_rec[FIT_REC_REASON] != 1.0) {                 // irregular: the general path from the start
+    HIPCHK(f, hipStreamSynchronize(f->st));
+    return 0;
+  }
+  adopt_fit_record(f, L.zero_copy, a.want_cov != 0);
   *info = f->conv_info_dev;
+  *status = *info ? 0 : ((int)f->nit >= f->opt.maxit ? LSQAMD_EMAXITER : -2);
   return 1;
 }
 

@@ -2,11 +2,34 @@
 // Trust Region Reflective and dogbox (box bounds), MINPACK's lmder.  Host-side step logic only --
 // every O(N P), O(P^2) and O(P^3) operation is one of the building blocks of eval.hip
 // (fit_state.h); the reference reaches these methods through src/lsqfit/_scipy.py:115-181.
-#include "fit_state.h"
+#include "host.h"
 
 using namespace lsqamd;
 
 namespace lsqamd_host {
+
+// ---- what trf and dogbox share (scipy optimize/_lsq/least_squares.py, common.py) --------------------------------
+// least_squares' own checks of the scaling, the tolerances and the start (name: "trf" / "dogbox"); no bounds: open ones
+static int scipy_check_start(lsqamd_fit *f, const char *name, const double *p0) {
+  if (f->opt.scaler == LSQAMD_SCALE_MARQUARDT)
+    FAIL(f, LSQAMD_EINVAL, "%s: x_scale is 1 (scaler levenberg) or 'jac' (scaler more)", name);
+  if (f->lb.empty()) { f->lb.assign(f->P, -INFINITY); f->ub.assign(f->P, INFINITY); }
+  if (f->opt.ftol < DBL_EPS && f->opt.xtol < DBL_EPS && f->opt.gtol < DBL_EPS)
+    FAIL(f, LSQAMD_EINVAL, "%s: at least one of the tolerances must be higher than machine epsilon", name);
+  for (int64_t j = 0; j < f->P; ++j)
+    if (!(p0[j] >= f->lb[j] && p0[j] <= f->ub[j]))
+      FAIL(f, LSQAMD_EINVAL, "%s: initial guess is outside of provided bounds (parameter %lld)", name, (long long)j);
+  return 0;
+}
+
+// actual over predicted reduction of the cost, as both methods define it
+static double scipy_ratio(double actual, double predicted) {
+  if (predicted > 0.0) return actual / predicted;
+  return predicted == 0.0 && actual == 0.0 ? 1.0 : 0.0;
+}
+
+// check_termination: 4 ftol and xtol, 2 ftol, 3 xtol; -1: go on
+static int scipy_status(bool f_ok, bool x_ok) { return f_ok && x_ok ? 4 : f_ok ? 2 : x_ok ? 3 : -1; }
 
 // ---- Trust Region Reflective with box bounds --------------------------
 // What src/lsqfit/_scipy.py:115-181 gets from scipy.optimize.least_squares(method='trf', bounds=...)
@@ -286,36 +309,46 @@ double trf_cl_scaling(const lsqamd_fit *f, std::vector<double> &v, std::vector<d
   return gn;
 }
 
-// trf_bounds / trf_no_bounds.  *status_out: 0 max_nfev, 1 gtol, 2 ftol, 3 xtol, 4 ftol and xtol
-int run_trf(lsqamd_fit *f, const double *p0, int *status_out) {
-  const int64_t P = f->P;
-  if (f->opt.scaler == LSQAMD_SCALE_MARQUARDT)
-    FAIL(f, LSQAMD_EINVAL, "trf: x_scale is 1 (scaler levenberg) or 'jac' (scaler more)");
-  if (f->lb.empty()) { f->lb.assign(P, -INFINITY); f->ub.assign(P, INFINITY); }
-  const double xtol = f->opt.xtol, gtol = f->opt.gtol, ftol = f->opt.ftol;
-  const double eps = 2.220446049250313e-16;
-  if (ftol < eps && xtol < eps && gtol < eps)
-    FAIL(f, LSQAMD_EINVAL, "trf: at least one of the tolerances must be higher than machine epsilon");
-  std::vector<double> x0(p0, p0 + P);
-  for (int64_t j = 0; j < P; ++j)
-    if (!(x0[j] >= f->lb[j] && x0[j] <= f->ub[j]))
-      FAIL(f, LSQAMD_EINVAL, "trf: initial guess is outside of provided bounds (parameter %lld)", (long long)j);
-  trf_feasible(f, x0, 1e-10);
-  int rc = do_init(f, x0.data());     // f, J, A = J^T J, g, column norms at x0; nfev = njev = 1
-  if (rc) return rc;
-  const int max_nfev = f->opt.maxit;
-  const bool jac_scale = f->opt.scaler == LSQAMD_SCALE_MORE;   // hdiag = 1 / scale (scale_init / scale_update)
-  std::vector<double> v(P), dv(P), p_h(P), step(P), step_h(P), x_new(P);
+// the first trust radius: |x_h| in the scaled variables at the start (1 if that is 0)
+static double trf_start_radius(const lsqamd_fit *f, std::vector<double> &v, std::vector<double> &dv) {
   (void)trf_cl_scaling(f, v, dv);
   double Delta = 0.0;
-  for (int64_t j = 0; j < P; ++j) {
+  for (int64_t j = 0; j < f->P; ++j) {
     if (dv[j] != 0.0) v[j] *= f->hdiag[j];
     const double t = f->hx[j] * f->hdiag[j] / std::sqrt(v[j]);
     Delta += t * t;
   }
   Delta = std::sqrt(Delta);
-  if (Delta == 0.0) Delta = 1.0;
-  double alpha = 0.0;
+  return Delta == 0.0 ? 1.0 : Delta;
+}
+
+// what stays fixed during the trial steps of an outer iteration, from the Coleman-Li scaling (v, dv, g_norm) at its point
+static void trf_begin_outer(const lsqamd_fit *f, TrfOuter &o, std::vector<double> &v, const std::vector<double> &dv, double g_norm) {
+  for (int64_t j = 0; j < f->P; ++j) {
+    if (dv[j] != 0.0) v[j] *= f->hdiag[j];
+    o.d[j] = std::sqrt(v[j]) / f->hdiag[j];
+    o.C[j] = f->hg[j] * dv[j] / f->hdiag[j];
+    o.gh[j] = o.d[j] * f->hg[j];
+  }
+  o.have_Aag = false;
+  o.gn_tried = false;
+  o.theta = std::fmax(0.995, 1.0 - g_norm);
+}
+
+// trf_bounds / trf_no_bounds.  *status_out: 0 max_nfev, 1 gtol, 2 ftol, 3 xtol, 4 ftol and xtol
+static int run_trf(lsqamd_fit *f, const double *p0, int *status_out) {
+  const int64_t P = f->P;
+  int rc = scipy_check_start(f, "trf", p0);
+  if (rc) return rc;
+  const double xtol = f->opt.xtol, gtol = f->opt.gtol, ftol = f->opt.ftol;
+  std::vector<double> x0(p0, p0 + P);
+  trf_feasible(f, x0, 1e-10);
+  rc = do_init(f, x0.data());     // f, J, A = J^T J, g, column norms at x0; nfev = njev = 1
+  if (rc) return rc;
+  const int max_nfev = f->opt.maxit;
+  const bool jac_scale = f->opt.scaler == LSQAMD_SCALE_MORE;   // hdiag = 1 / scale (scale_init / scale_update)
+  std::vector<double> v(P), dv(P), p_h(P), step(P), step_h(P), x_new(P);
+  double Delta = trf_start_radius(f, v, dv), alpha = 0.0;
   int status = -1;
   TrfOuter o;
   o.d.resize(P); o.C.resize(P); o.gh.resize(P);
@@ -325,17 +358,9 @@ int run_trf(lsqamd_fit *f, const double *p0, int *status_out) {
     if (trace) fprintf(stderr, "trf nfev %d cost %.12e optimality %.3e Delta %.3e alpha %.3e\n", f->nfev, 0.5 * f->chi2, g_norm, Delta, alpha);
     if (g_norm < gtol) status = 1;
     if (status >= 0 || f->nfev >= max_nfev) break;
-    for (int64_t j = 0; j < P; ++j) {
-      if (dv[j] != 0.0) v[j] *= f->hdiag[j];
-      o.d[j] = std::sqrt(v[j]) / f->hdiag[j];
-      o.C[j] = f->hg[j] * dv[j] / f->hdiag[j];
-      o.gh[j] = o.d[j] * f->hg[j];
-    }
-    o.have_Aag = false;
-    o.gn_tried = false;
-    o.theta = std::fmax(0.995, 1.0 - g_norm);
+    trf_begin_outer(f, o, v, dv, g_norm);
     const double cost = 0.5 * f->chi2;
-    double actual = -1.0, cost_new = cost;
+    double actual = -1.0;
     while (actual <= 0.0 && f->nfev < max_nfev) {
       double quad = 0.0, predicted = 0.0;
       rc = trf_subproblem(f, o, Delta, &alpha, p_h, &quad);
@@ -344,42 +369,31 @@ int run_trf(lsqamd_fit *f, const double *p0, int *status_out) {
       if (rc) return rc;
       for (int64_t j = 0; j < P; ++j) x_new[j] = f->hx[j] + step[j];
       trf_feasible(f, x_new, 0.0);
-      std::memcpy(f->pin_x, x_new.data(), sizeof(double) * P);
-      HIPCHK(f, hipMemcpyAsync(f->p_trial, f->pin_x, sizeof(double) * P, hipMemcpyHostToDevice, f->st));
       double chi2_new = 0.0;
-      rc = eval_residual_dev(f, f->p_trial, &chi2_new);
+      rc = trial_residual(f, x_new.data(), &chi2_new);
       if (rc) return rc;
       const double sh_norm = norm_h(step_h);
       if (!std::isfinite(chi2_new)) {
         Delta = 0.25 * sh_norm;
         continue;
       }
-      cost_new = 0.5 * chi2_new;
-      actual = cost - cost_new;
-      double ratio;
-      if (predicted > 0.0) ratio = actual / predicted;
-      else if (predicted == 0.0 && actual == 0.0) ratio = 1.0;
-      else ratio = 0.0;
+      actual = cost - 0.5 * chi2_new;
+      const double ratio = scipy_ratio(actual, predicted);
       double Delta_new = Delta;
       if (ratio < 0.25) Delta_new = 0.25 * sh_norm;
       else if (ratio > 0.75 && sh_norm > 0.95 * Delta) Delta_new = 2.0 * Delta;
       const bool f_ok = actual < ftol * cost && ratio > 0.25;
       const bool x_ok = norm_h(step) < xtol * (xtol + norm_h(f->hx));
       if (trace) fprintf(stderr, "    trial: actual %.3e predicted %.3e ratio %.3f |step_h| %.3e Delta %.3e -> %.3e\n", actual, predicted, ratio, sh_norm, Delta, Delta_new);
-      if (f_ok && x_ok) status = 4;
-      else if (f_ok) status = 2;
-      else if (x_ok) status = 3;
+      status = scipy_status(f_ok, x_ok);
       if (status >= 0) break;
       alpha *= Delta / Delta_new;
       Delta = Delta_new;
     }
     if (actual > 0.0) {
-      rc = eval_normal_dev(f, f->p_trial);
+      rc = accept_trial(f, x_new, jac_scale);
       if (rc) return rc;
-      f->hx = x_new;
       f->hdx = step;
-      std::swap(f->p_dev, f->p_trial);
-      if (jac_scale) scale_update(f);
     }
   }
   *status_out = status < 0 ? 0 : status;
@@ -452,20 +466,42 @@ void dogbox_step(const std::vector<double> &x, const std::vector<double> &newton
   *beta_g = -t_c * (1.0 - t);
 }
 
-int run_dogbox(lsqamd_fit *f, const double *p0, int *status_out) {
-  const int64_t P = f->P;
-  if (f->opt.scaler == LSQAMD_SCALE_MARQUARDT)
-    FAIL(f, LSQAMD_EINVAL, "dogbox: x_scale is 1 (scaler levenberg) or 'jac' (scaler more)");
-  if (f->lb.empty()) { f->lb.assign(P, -INFINITY); f->ub.assign(P, INFINITY); }
-  const double xtol = f->opt.xtol, gtol = f->opt.gtol, ftol = f->opt.ftol;
-  const double eps = 2.220446049250313e-16;
-  if (ftol < eps && xtol < eps && gtol < eps)
-    FAIL(f, LSQAMD_EINVAL, "dogbox: at least one of the tolerances must be higher than machine epsilon");
-  for (int64_t j = 0; j < P; ++j)
-    if (!(p0[j] >= f->lb[j] && p0[j] <= f->ub[j]))
-      FAIL(f, LSQAMD_EINVAL, "dogbox: initial guess is outside of provided bounds (parameter %lld)", (long long)j);
-  int rc = do_init(f, p0);
+// the active set at the current point (on its wall, gradient pointing outwards) -> free_set, frozen, the gradient zeroed on
+// it (gz), whether there is any; returns |gz|_inf
+static double dogbox_active_set(const lsqamd_fit *f, const std::vector<int> &on_bound, std::vector<char> &free_set,
+                                std::vector<double> &frozen, std::vector<double> &gz, bool *any_active) {
+  double g_norm = 0.0;
+  for (int64_t j = 0; j < f->P; ++j) {
+    const bool active = on_bound[j] * f->hg[j] < 0.0;
+    free_set[j] = !active;
+    frozen[j] = active ? 1.0 : 0.0;
+    *any_active |= active;
+    gz[j] = active ? 0.0 : f->hg[j];
+    g_norm = std::fmax(g_norm, std::fabs(gz[j]));
+  }
+  return g_norm;
+}
+
+// the outer iteration's one factorisation and one product: the Gauss-Newton step of the free parameters and g.A g, g.g, n.g
+static int dogbox_newton(lsqamd_fit *f, const double *frozen, const std::vector<char> &free_set, const std::vector<double> &gz,
+                         std::vector<double> &newton, double *gAg, double *gg, double *ng) {
+  int rc = solve_damped_dev(f, 0.0, nullptr, frozen);
+  if (rc == LSQAMD_ENOTPD)
+    FAIL(f, LSQAMD_ENOTPD, "dogbox: J^T J of the free parameters is not positive definite (rank-deficient Jacobian)");
   if (rc) return rc;
+  for (int64_t j = 0; j < f->P; ++j) newton[j] = free_set[j] ? -f->hv[j] : 0.0;
+  std::vector<double> Ag(f->P);
+  rc = symv_host(f, gz.data(), Ag.data());
+  if (rc) return rc;
+  *gAg = dot_h(gz, Ag); *gg = dot_h(gz, gz); *ng = dot_h(newton, gz);
+  return 0;
+}
+
+static int run_dogbox(lsqamd_fit *f, const double *p0, int *status_out) {
+  const int64_t P = f->P;
+  int rc = scipy_check_start(f, "dogbox", p0);
+  if (rc || (rc = do_init(f, p0))) return rc;
+  const double xtol = f->opt.xtol, gtol = f->opt.gtol, ftol = f->opt.ftol;
   const int max_nfev = f->opt.maxit;
   const bool jac_scale = f->opt.scaler == LSQAMD_SCALE_MORE;   // hdiag = 1 / scale
   double Delta = 0.0;
@@ -477,29 +513,16 @@ int run_dogbox(lsqamd_fit *f, const double *p0, int *status_out) {
     if (f->hx[j] == f->ub[j]) on_bound[j] = 1;
   }
   std::vector<char> free_set(P, 1);
-  std::vector<double> gz(P), frozen(P), newton(P), Ag(P), step(P), x_new(P);
+  std::vector<double> gz(P), frozen(P), newton(P), step(P), x_new(P);
   int status = -1;
   while (true) {
     bool any_active = false;
-    double g_norm = 0.0;
-    for (int64_t j = 0; j < P; ++j) {
-      const bool active = on_bound[j] * f->hg[j] < 0.0;
-      free_set[j] = !active;
-      frozen[j] = active ? 1.0 : 0.0;
-      any_active |= active;
-      gz[j] = active ? 0.0 : f->hg[j];
-      g_norm = std::fmax(g_norm, std::fabs(gz[j]));
-    }
+    const double g_norm = dogbox_active_set(f, on_bound, free_set, frozen, gz, &any_active);
     if (g_norm < gtol) status = 1;
     if (status >= 0 || f->nfev >= max_nfev) break;
-    rc = solve_damped_dev(f, 0.0, nullptr, any_active ? frozen.data() : nullptr);
-    if (rc == LSQAMD_ENOTPD)
-      FAIL(f, LSQAMD_ENOTPD, "dogbox: J^T J of the free parameters is not positive definite (rank-deficient Jacobian)");
+    double gAg = 0.0, gg = 0.0, ng = 0.0;
+    rc = dogbox_newton(f, any_active ? frozen.data() : nullptr, free_set, gz, newton, &gAg, &gg, &ng);
     if (rc) return rc;
-    for (int64_t j = 0; j < P; ++j) newton[j] = free_set[j] ? -f->hv[j] : 0.0;
-    rc = symv_host(f, gz.data(), Ag.data());
-    if (rc) return rc;
-    const double gAg = dot_h(gz, Ag), gg = dot_h(gz, gz), ng = dot_h(newton, gz);
     const double a = 0.5 * gAg, b = -gg;
     const double nAn = -ng, nAg = -gg;      // (A n)_free = -g_free
     const double cost = 0.5 * f->chi2;
@@ -518,27 +541,20 @@ int run_dogbox(lsqamd_fit *f, const double *p0, int *status_out) {
         s_norm += step[j] * step[j];
       }
       s_norm = std::sqrt(s_norm);
-      std::memcpy(f->pin_x, x_new.data(), sizeof(double) * P);
-      HIPCHK(f, hipMemcpyAsync(f->p_trial, f->pin_x, sizeof(double) * P, hipMemcpyHostToDevice, f->st));
       double chi2_new = 0.0;
-      rc = eval_residual_dev(f, f->p_trial, &chi2_new);
+      rc = trial_residual(f, x_new.data(), &chi2_new);
       if (rc) return rc;
       if (!std::isfinite(chi2_new)) {
         Delta = 0.25 * sh_norm;
         continue;
       }
       actual = cost - 0.5 * chi2_new;
-      double ratio;
-      if (predicted > 0.0) ratio = actual / predicted;
-      else if (predicted == 0.0 && actual == 0.0) ratio = 1.0;
-      else ratio = 0.0;
+      const double ratio = scipy_ratio(actual, predicted);
       if (ratio < 0.25) Delta = 0.25 * sh_norm;
       else if (ratio > 0.75 && tr_hit) Delta *= 2.0;
       const bool f_ok = actual < ftol * cost && ratio > 0.25;
       const bool x_ok = s_norm < xtol * (xtol + norm_h(f->hx));
-      if (f_ok && x_ok) status = 4;
-      else if (f_ok) status = 2;
-      else if (x_ok) status = 3;
+      status = scipy_status(f_ok, x_ok);
       if (status >= 0) break;
     }
     if (actual > 0.0) {
@@ -547,14 +563,9 @@ int run_dogbox(lsqamd_fit *f, const double *p0, int *status_out) {
         if (on_bound[j] == -1) x_new[j] = f->lb[j];
         if (on_bound[j] == 1) x_new[j] = f->ub[j];
       }
-      std::memcpy(f->pin_x, x_new.data(), sizeof(double) * P);   // variables set exactly on their walls
-      HIPCHK(f, hipMemcpyAsync(f->p_trial, f->pin_x, sizeof(double) * P, hipMemcpyHostToDevice, f->st));
-      rc = eval_normal_dev(f, f->p_trial);
-      if (rc) return rc;
-      f->hx = x_new;
+      rc = upload_point(f, f->p_trial, x_new.data());   // variables set exactly on their walls
+      if (rc || (rc = accept_trial(f, x_new, jac_scale))) return rc;
       f->hdx = step;
-      std::swap(f->p_dev, f->p_trial);
-      if (jac_scale) scale_update(f);
     }
   }
   *status_out = status < 0 ? 0 : status;
@@ -642,21 +653,26 @@ int lmpar_dev(lsqamd_fit *f, LmparOuter &o, double delta, double *par_io, std::v
   return 0;
 }
 
-// lmder.  *status_out in scipy's numbering (FROM_MINPACK_TO_COMMON): info 1, 2, 3, 4, 5 -> 2, 3, 4, 1, 0
-int run_minpack(lsqamd_fit *f, const double *p0, int *status_out) {
-  const int64_t P = f->P;
+// least_squares' checks for method 'lm': the scaling, every tolerance above machine epsilon, no finite bound
+static int minpack_check_start(lsqamd_fit *f) {
   if (f->opt.scaler == LSQAMD_SCALE_MARQUARDT)
     FAIL(f, LSQAMD_EINVAL, "minpack lm: x_scale is 1 (scaler levenberg) or 'jac' (scaler more)");
-  const double xtol = f->opt.xtol, gtol = f->opt.gtol, ftol = f->opt.ftol;
-  const double epsmch = 2.220446049250313e-16, factor = 100.0;
-  if (ftol < epsmch || xtol < epsmch || gtol < epsmch)
+  if (f->opt.ftol < DBL_EPS || f->opt.xtol < DBL_EPS || f->opt.gtol < DBL_EPS)
     FAIL(f, LSQAMD_EINVAL, "minpack lm: all tolerances must be higher than machine epsilon");
   if (!f->lb.empty())
-    for (int64_t j = 0; j < P; ++j)
+    for (int64_t j = 0; j < f->P; ++j)
       if (std::isfinite(f->lb[j]) || std::isfinite(f->ub[j]))
         FAIL(f, LSQAMD_EINVAL, "minpack lm: method 'lm' doesn't support bounds");
-  int rc = do_init(f, p0);   // fvec, J, A, g, column norms, D (mode 1: column norms, 1 where 0); nfev = njev = 1
-  if (rc) return rc;
+  return 0;
+}
+
+// lmder.  *status_out in scipy's numbering (FROM_MINPACK_TO_COMMON): info 1, 2, 3, 4, 5 -> 2, 3, 4, 1, 0
+static int run_minpack(lsqamd_fit *f, const double *p0, int *status_out) {
+  const int64_t P = f->P;
+  const double xtol = f->opt.xtol, gtol = f->opt.gtol, ftol = f->opt.ftol;
+  const double epsmch = DBL_EPS, factor = 100.0;
+  int rc = minpack_check_start(f);
+  if (rc || (rc = do_init(f, p0))) return rc;   // fvec, J, A, g, column norms, D (mode 1: column norms, 1 where 0); nfev = njev = 1
   const int maxfev = f->opt.maxit;
   const bool mode1 = f->opt.scaler == LSQAMD_SCALE_MORE;
   double fnorm = std::sqrt(f->chi2);
@@ -680,10 +696,8 @@ int run_minpack(lsqamd_fit *f, const double *p0, int *status_out) {
       for (int64_t j = 0; j < P; ++j) { xt[j] = f->hx[j] - p[j]; pg += p[j] * f->hg[j]; }
       const double pnorm = scaled_norm(f->hdiag, p);
       if (iter == 1) delta = std::fmin(delta, pnorm);
-      std::memcpy(f->pin_x, xt.data(), sizeof(double) * P);
-      HIPCHK(f, hipMemcpyAsync(f->p_trial, f->pin_x, sizeof(double) * P, hipMemcpyHostToDevice, f->st));
       double chi2_t = 0.0;
-      rc = eval_residual_dev(f, f->p_trial, &chi2_t);
+      rc = trial_residual(f, xt.data(), &chi2_t);
       if (rc) return rc;
       const double fnorm1 = std::sqrt(chi2_t);     // NaN compares false everywhere below: rejected
       double actred = -1.0;
@@ -704,13 +718,10 @@ int run_minpack(lsqamd_fit *f, const double *p0, int *status_out) {
       }
       const bool accepted = ratio >= 1e-4;
       if (accepted) {
-        rc = eval_normal_dev(f, f->p_trial);    // also the Jacobian of the next outer pass
+        xnorm = scaled_norm(f->hdiag, xt);      // with the D of this pass (lmder.f): accept_trial updates it
+        rc = accept_trial(f, xt, mode1);        // also the Jacobian of the next outer pass
         if (rc) return rc;
-        f->hx = xt;
         for (int64_t j = 0; j < P; ++j) f->hdx[j] = -p[j];
-        std::swap(f->p_dev, f->p_trial);
-        xnorm = scaled_norm(f->hdiag, f->hx);   // with the D of this pass (lmder.f), before its update
-        if (mode1) scale_update(f);
         fnorm = fnorm1;
         ++iter;
       }
@@ -731,6 +742,24 @@ int run_minpack(lsqamd_fit *f, const double *p0, int *status_out) {
   // place (one evaluation more than MINPACK counts -- the caller needs J there anyway, _scipy.py:160)
   static const int to_scipy[9] = {-1, 2, 3, 4, 1, 0, 2, 3, 1};   // 6, 7, 8: the tests 1, 2, 4 at machine precision
   *status_out = to_scipy[info];
+  return 0;
+}
+
+// lsqamd_run for the three methods: what scipy and this library refuse for all of them, then the method
+int run_scipy_method(lsqamd_fit *f, const double *p0, int *status, int *info) {
+  const int trs = f->opt.trs;
+  if (f->loss != LSQAMD_LOSS_LINEAR && trs == LSQAMD_TRS_MINPACK_LM)
+    FAIL(f, LSQAMD_EINVAL, "method='lm' supports only 'linear' loss function.");      // scipy's wording
+  if (f->robust() && f->cfg.has_prior)
+    FAIL(f, LSQAMD_EUNSUPPORTED, "a robust loss acts on residual rows: pass the prior as rows (lsqamd_set_param_rows), not through lsqamd_set_prior");
+  if (f->robust() && (f->comm || f->reduce))
+    FAIL(f, LSQAMD_EUNSUPPORTED, "robust losses are single-rank");
+  int st = 0;
+  const int rc = trs == LSQAMD_TRS_TRF ? run_trf(f, p0, &st) : trs == LSQAMD_TRS_DOGBOX ? run_dogbox(f, p0, &st) : run_minpack(f, p0, &st);
+  if (rc) return rc;
+  f->nit = f->nfev;                      // _scipy.py:161: nit = number of function evaluations
+  *info = LSQAMD_INFO_TRF + st;
+  *status = 0;
   return 0;
 }
 
