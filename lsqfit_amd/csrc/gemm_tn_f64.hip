@@ -269,7 +269,11 @@ template <bool XTRI, bool WORKMAP, bool CS = false, bool SIGNAL = false>
 __global__ __launch_bounds__(256, 2) void gemm_tn_f64_interior_kernel(GemmDev g) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
+  // Uniform control: the wave index and the work-list entry are the same in every lane, but the compiler cannot see that
+  // (tid >> 6; a per-lane load), so they are made uniform by hand.  Everything derived from them -- m0, n0, kb, ke, the
+  // diagonal role, the C base, the operand row bases, the LDS destinations of the staging loads -- then lives in scalar
+  // registers and the k loop's control is scalar compares on a 32-bit stage count.
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   int tm, tn, split;
   int sig_group = 0;
@@ -286,8 +290,10 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_f64_interior_kernel(GemmDev g)
     stamp_w = w;
 #endif
     const int4 e = reinterpret_cast<const int4 *>(g.work_map)[w];
-    tm = e.x; tn = e.y; split = e.z;
-    if (SIGNAL) sig_group = e.w;
+    tm = __builtin_amdgcn_readfirstlane(e.x);
+    tn = __builtin_amdgcn_readfirstlane(e.y);
+    split = __builtin_amdgcn_readfirstlane(e.z);
+    if (SIGNAL) sig_group = __builtin_amdgcn_readfirstlane(e.w);
   } else if (XTRI && g.xcd_groups) {
     // Workgroup b runs on XCD b % 8.  With the tile column as the fastest index (and 8 of them) every XCD would own ONE
     // tile column and read ALL of X for it -- config 3's triangular whitening matrix went past the L2 eight times (L2 hit
@@ -349,21 +355,31 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_f64_interior_kernel(GemmDev g)
   // wave w stages rows w, w+4, w+8, w+12 of both tiles; lane -> 2 columns
   typedef __attribute__((address_space(3))) void lds_void;
   typedef const __attribute__((address_space(1))) void glb_void;
-  const double *xp = g.X + b * g.sx + (kb + wave) * g.ldx + m0 + 2 * lane;
-  const double *yp = g.Y + b * g.sy + (kb + wave) * g.ldy + n0 + 2 * lane;
-  const int64_t xstep = 4 * g.ldx, ystep = 4 * g.ldy;
+  // (xb, yb: uniform row bases, advanced per stage on the scalar unit; lane_off: this lane's 16 bytes of a row)
+  const char *xb = reinterpret_cast<const char *>(g.X + b * g.sx + (kb + wave) * g.ldx + m0);
+  const char *yb = reinterpret_cast<const char *>(g.Y + b * g.sy + (kb + wave) * g.ldy + n0);
+  const int64_t xstep = 4 * g.ldx * (int64_t)sizeof(double), ystep = 4 * g.ldy * (int64_t)sizeof(double);
+  uint32_t lane_off = 16u * (uint32_t)lane;
+  const int nst = kb < ke ? (int)((ke - kb + BK - 1) >> 4) : 0;   // K stages of this entry (BK = 16)
   // CS: lanes 0..31 of wave 1 fetch the 16 residuals of a stage as 32 dwords (lane -> row lane / 2, half lane & 1)
   const char *fp = reinterpret_cast<const char *>(g.X + b * g.sx + (kb + (lane >> 1)) * g.ldx + g.colsum_rcol) + 4 * (lane & 1);
   const int64_t fstep = (int64_t)BK * g.ldx * (int64_t)sizeof(double);
   double cs = 0.0, cs2 = 0.0;
 
-  auto stage = [&](int buf) {
+  // Staging addresses: uniform row base + loop-invariant 32-bit lane offset.  The builtin is enough: with the address in
+  // this form the compiler picks the scalar-base encoding (global_load_lds_dwordx4 v_off, s[base:base+1]) and, the
+  // buffer index being a compile-time value and `wave` uniform, each LDS destination is a scalar moved to m0.  The
+  // encoding is chosen per basic block and only when the 32 -> 64-bit extension of the lane offset is in the block of
+  // the load: the empty statement (no instruction) redefines lane_off here so that the extension is not hoisted.
+  auto stage = [&](auto buf_tag) {
+    constexpr int buf = decltype(buf_tag)::value;
+    asm volatile("" : "+v"(lane_off));
     double *Xs = smem + buf * STAGE + wave * LDT;
     double *Ys = Xs + BK * LDT;
     if (diag) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        __builtin_amdgcn_global_load_lds((glb_void *)(xp + i * xstep), (lds_void *)(Xs + 4 * i * LDT), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((glb_void *)(xb + i * xstep + lane_off), (lds_void *)(Xs + 4 * i * LDT), 16, 0, 0);
       if (CS && wave == 1) {
         if (lane < 32)
           __builtin_amdgcn_global_load_lds((glb_void *)fp, (lds_void *)(smem + buf * STAGE + BK * LDT), 4, 0, 0);
@@ -372,12 +388,12 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_f64_interior_kernel(GemmDev g)
     } else {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        __builtin_amdgcn_global_load_lds((glb_void *)(xp + i * xstep), (lds_void *)(Xs + 4 * i * LDT), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((glb_void *)(yp + i * ystep), (lds_void *)(Ys + 4 * i * LDT), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((glb_void *)(xb + i * xstep + lane_off), (lds_void *)(Xs + 4 * i * LDT), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((glb_void *)(yb + i * ystep + lane_off), (lds_void *)(Ys + 4 * i * LDT), 16, 0, 0);
       }
     }
-    xp += 4 * xstep;
-    yp += 4 * ystep;
+    xb += 4 * xstep;
+    yb += 4 * ystep;
   };
 
   // weights of the fused column sums: fetched now, used in the epilogue (latency hidden by the k loop)
@@ -385,32 +401,66 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_f64_interior_kernel(GemmDev g)
   double wreg = 0.0;
   if (fuse && tid < BM) wreg = (g.C + b * g.sc)[(m0 + tid) * g.ldc + g.colsum_rcol];
   const int fr = lane & 15, fq = lane >> 4;
-  if (kb < ke) stage(0);
+  if (nst > 0) stage(std::integral_constant<int, 0>{});
   __syncthreads();
   // ROLE 0: all 16 sub-tiles; 1: sub-tiles i <= j (diagonal quadrant of a diagonal tile); 2: strips i < 2
   auto kloop = [&](auto role_tag) {
     constexpr int ROLE = decltype(role_tag)::value;
-    int cur = 0;
-    for (int64_t k0 = kb; k0 < ke; k0 += BK) {
-      if (k0 + BK < ke) stage(cur ^ 1);
-      const double *Xs = smem + cur * STAGE;
-      const double *Ys = ROLE == 0 ? Xs + BK * LDT : Xs;
+    // fragment bases per (buffer, k-step): a k-step is 4608 bytes, beyond the reach of a ds_read2_b64 offset, so each gets
+    // its own address register, set once (the empty statements keep the compiler from recomputing them in every stage)
+    typedef const __attribute__((address_space(3))) double lds_cdouble;
+    lds_cdouble *ap[2][BK / 4], *bp[2][BK / 4];
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
 #pragma unroll
       for (int kk = 0; kk < BK / 4; ++kk) {
-        const int kr = kk * 4 + fq;
-        double a[4], bb[4];
+        const double *Xk = smem + c * STAGE + (kk * 4 + fq) * LDT + fr;
+        ap[c][kk] = (lds_cdouble *)(Xk + (XTRI ? wm * 16 : arow0));
+        bp[c][kk] = (lds_cdouble *)(Xk + (ROLE == 0 ? BK * LDT : 0) + bcol0);
+        asm volatile("" : "+v"(ap[c][kk]), "+v"(bp[c][kk]));
+      }
+    // one K stage out of buffer `cur` (a compile-time value: the LDS reads are base register + immediate)
+    // TRI (XTRI only): 0 = a full stage, every strip takes every k-step; 1 = stage ts = 0..7 of the tile row's own 128
+    // k-values, k0 = m0 + 16 ts.  X[k][m] = 0 for k > m: strip t = 2 i + wm (rows m0 + 16 t .. + 15) sees nothing from
+    // k-steps k0 + 4 kk > m0 + 16 t + 15, i.e. it takes all four k-steps of the stage when t >= ts and none otherwise.
+    // One 32-bit test of uniform values per strip (a scalar compare and branch) with the strip as the outer loop: every
+    // accumulator still receives its k-steps in ascending order, so the sums are the same.
+    auto body = [&](auto cur_tag, auto tri_tag, const int ts, const bool more) {
+      constexpr int cur = decltype(cur_tag)::value;
+      constexpr bool TRI = XTRI && decltype(tri_tag)::value != 0;
+      if (more) stage(std::integral_constant<int, cur ^ 1>{});
+      const double *Xs = smem + cur * STAGE;
+      if (TRI) {
+        double bb[BK / 4][4];
 #pragma unroll
-        for (int i = 0; i < (ROLE == 2 ? 2 : 4); ++i)
-          a[i] = Xs[kr * LDT + (XTRI ? (2 * i + wm) * 16 : arow0 + i * 16) + fr];
+        for (int kk = 0; kk < BK / 4; ++kk)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) bb[j] = Ys[kr * LDT + bcol0 + j * 16 + fr];
+          for (int j = 0; j < 4; ++j) bb[kk][j] = bp[cur][kk][j * 16];
 #pragma unroll
-        for (int i = 0; i < (ROLE == 2 ? 2 : 4); ++i) {
-          // X[k][m] = 0 for k > m: strip rows m0 + 16 s .. + 15 see nothing from k-steps beyond them
-          if (XTRI && k0 + kk * 4 > m0 + (2 * i + wm) * 16 + 15) continue;
+        for (int i = 0; i < 4; ++i) {
+          if (2 * i + wm < ts) continue;
+          double a[BK / 4];
 #pragma unroll
-          for (int j = (ROLE == 1 ? i : 0); j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], bb[j], acc[i][j], 0, 0, 0);
+          for (int kk = 0; kk < BK / 4; ++kk) a[kk] = ap[cur][kk][2 * i * 16];
+#pragma unroll
+          for (int kk = 0; kk < BK / 4; ++kk)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], bb[kk][j], acc[i][j], 0, 0, 0);
+        }
+      } else {
+#pragma unroll
+        for (int kk = 0; kk < BK / 4; ++kk) {
+          double a[4], bb[4];
+#pragma unroll
+          for (int i = 0; i < (ROLE == 2 ? 2 : 4); ++i) a[i] = ap[cur][kk][(XTRI ? 2 * i : i) * 16];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) bb[j] = bp[cur][kk][j * 16];
+#pragma unroll
+          for (int i = 0; i < (ROLE == 2 ? 2 : 4); ++i)
+#pragma unroll
+            for (int j = (ROLE == 1 ? i : 0); j < 4; ++j)
+              acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], bb[j], acc[i][j], 0, 0, 0);
         }
       }
       if (CS && ROLE != 0) {   // thread -> column tid & 127, rows 8 (tid >> 7) .. + 7 of the stage
@@ -424,7 +474,36 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_f64_interior_kernel(GemmDev g)
         }
       }
       __syncthreads();
-      cur ^= 1;
+    };
+    // the full stages (all of them unless XTRI; XTRI: those below the tile row's own k-values, k0 + BK <= m0): the loop
+    // unrolled by two (buffers 0, 1), then the peeled last stage of an odd count (a one-stage entry is that stage alone)
+    using c0_tag = std::integral_constant<int, 0>;
+    using c1_tag = std::integral_constant<int, 1>;
+    int nfull = nst;
+    if (XTRI) {
+      const int64_t below = kb < m0 ? (m0 - kb) >> 4 : 0;
+      nfull = below < nst ? (int)below : nst;
+    }
+    int s = 0;
+    for (; s + 1 < nfull; s += 2) {
+      body(c0_tag{}, c0_tag{}, 0, true);
+      body(c1_tag{}, c0_tag{}, 0, s + 2 < nst);
+    }
+    if (s < nfull) body(c0_tag{}, c0_tag{}, 0, s + 1 < nst);
+    if (XTRI && nfull < nst) {
+      // the (up to eight) triangular stages t0 .. t1 - 1 (stages past the eighth would multiply zeros only), again
+      // unrolled by two: first one stage out of buffer 1 if that is where the full stages ended
+      const int t1 = (int)((kb + (int64_t)nst * BK - m0) >> 4);
+      int t = t1 - (nst - nfull);
+      if (nfull & 1) {
+        body(c1_tag{}, c1_tag{}, t, t + 1 < t1);
+        ++t;
+      }
+      for (; t + 1 < t1; t += 2) {
+        body(c0_tag{}, c1_tag{}, t, true);
+        body(c1_tag{}, c1_tag{}, t + 1, t + 2 < t1);
+      }
+      if (t < t1) body(c0_tag{}, c1_tag{}, t, false);
     }
   };
   if (WORKMAP && !XTRI && diag) {
@@ -1227,7 +1306,10 @@ __global__ __launch_bounds__(256, 2) void whiten_synth_kernel(WhitenSynth a, int
   extern __shared__ __attribute__((aligned(16))) double smem[];
   if (a.trig_far && (a.trig_far[0] != 0) != FAR) return;    // (FAR = false: no far-range trig code, see model.hip)
   const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform: the triangular skips become scalar branches)
+  // (wave made uniform: the staging destinations and the strip tests of the triangular stages are scalar.  A uniform value
+  // alone does not make a branch scalar: while the skips compared 64-bit k indices they were vector compares and vcc
+  // branches -- the scalar unit has no ordered 64-bit compare -- which is why mfmas_tri below tests a 32-bit stage index.)
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int tm_first = blockIdx.x / tiles_n, tn = blockIdx.x % tiles_n;
   // pair_rows (blocks of many tile rows: the k-range of a tile row grows with it): this workgroup does tile
@@ -1238,7 +1320,6 @@ __global__ __launch_bounds__(256, 2) void whiten_synth_kernel(WhitenSynth a, int
   const int tm = pass == 0 ? tm_first : tiles_m - 1 - tm_first;
   const int64_t b = blockIdx.z;
   const int64_t m0 = (int64_t)tm * BM;
-  const int64_t ke = m0 + BM;                     // X[k][m] = 0 for k > m
   const double *Xb = a.Wt + b * a.B * a.B;
   const double *xrow = a.x + b * a.B;
   double *C = a.J + b * a.B * a.ld;
@@ -1254,29 +1335,34 @@ __global__ __launch_bounds__(256, 2) void whiten_synth_kernel(WhitenSynth a, int
     for (int j = 0; j < NJ; ++j) acc[i][j] = (v4d){0.0, 0.0, 0.0, 0.0};
   typedef __attribute__((address_space(3))) void lds_void;
   typedef const __attribute__((address_space(1))) void glb_void;
-  const double *xp = Xb + (int64_t)wave * a.B + m0 + 2 * lane;
-  const int64_t xstep = 4 * a.B;
+  const char *xb = reinterpret_cast<const char *>(Xb + (int64_t)wave * a.B + m0);
+  const int64_t xstep = 4 * a.B * (int64_t)sizeof(double);
+  uint32_t lane_off = 16u * (uint32_t)lane;
   // abscissae of the stage rows: a ring of three 32-double slots in LDS, slot s % 3 = x[16 s .. 16 s + 31],
   // filled two stages ahead by one 256-byte DMA of wave 0 -- no register ever waits on a global load in
   // the loop (vmcnt retires in order: a wait for x would be a wait for the operand rows behind it)
   double *xring = smem + 2 * STAGE;
-  auto xdma = [&](int64_t sidx) {
+  auto xdma = [&](int sidx) {
     if (wave == 0) {
-      int64_t e = sidx * BK + (lane >> 1);
+      int64_t e = (int64_t)sidx * BK + (lane >> 1);
       if (e > a.B - 1) e = a.B - 1;
       const char *src = reinterpret_cast<const char *>(xrow + e) + 4 * (lane & 1);
       __builtin_amdgcn_global_load_lds((glb_void *)src, (lds_void *)(xring + (sidx % 3) * 32), 4, 0, 0);
     }
   };
-  int64_t ssyn = 0;     // index of the stage `stage_synth` builds next
-  auto stage_dma = [&](int buf) {
+  int ssyn = 0;         // index of the stage `stage_synth` builds next
+  // (uniform row base + 32-bit lane offset, as in gemm_tn_f64_interior_kernel: see the comment at its staging lambda)
+  auto stage_dma = [&](auto buf_tag) {
+    constexpr int buf = decltype(buf_tag)::value;
+    asm volatile("" : "+v"(lane_off));
     double *Xs = smem + buf * STAGE + wave * LDT;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_global_load_lds((glb_void *)(xp + i * xstep), (lds_void *)(Xs + 4 * i * LDT), 16, 0, 0);
-    xp += 4 * xstep;
+      __builtin_amdgcn_global_load_lds((glb_void *)(xb + i * xstep + lane_off), (lds_void *)(Xs + 4 * i * LDT), 16, 0, 0);
+    xb += 4 * xstep;
   };
-  auto stage_synth = [&](int buf) {
+  auto stage_synth = [&](auto buf_tag) {
+    constexpr int buf = decltype(buf_tag)::value;
     double xs4[NS];
     const double *xq = xring + (ssyn % 3) * 32 + srow;
 #pragma unroll
@@ -1304,19 +1390,28 @@ __global__ __launch_bounds__(256, 2) void whiten_synth_kernel(WhitenSynth a, int
   };
   const double wreg = (tid < BM) ? C[(m0 + tid) * a.ld + 2 * a.K] : 0.0;   // whitened residual of this tile's rows
   const int fr = lane & 15, fq = lane >> 4;
+  using c0_tag = std::integral_constant<int, 0>;
+  using c1_tag = std::integral_constant<int, 1>;
   xdma(0);
   xdma(1);
-  stage_dma(0);          // the first operand rows travel together with the abscissae: one exposed latency, not two
+  stage_dma(c0_tag{});   // the first operand rows travel together with the abscissae: one exposed latency, not two
   __syncthreads();
-  stage_synth(0);
+  stage_synth(c0_tag{});
   __syncthreads();
-  int cur = 0;
-  for (int64_t k0 = 0; k0 < ke; k0 += BK) {
-    if (k0 + BK < ke) {
-      if (k0 + 2 * BK < ke) xdma(k0 / BK + 2);
-      stage_dma(cur ^ 1);
-      stage_synth(cur ^ 1);
+  // A K stage out of buffer `cur` (a compile-time value: LDS addresses are base register + immediate) is `next`, the DMA
+  // and the synthesis of the stage after it into the other buffer, then the MFMAs, then the barrier.
+  const int nst = 8 * (tm + 1);
+  auto next = [&](auto cur_tag, const int sidx) {
+    constexpr int cur = decltype(cur_tag)::value;
+    if (sidx + 1 < nst) {
+      if (sidx + 2 < nst) xdma(sidx + 2);
+      stage_dma(std::integral_constant<int, cur ^ 1>{});
+      stage_synth(std::integral_constant<int, cur ^ 1>{});
     }
+  };
+  // full stage (k0 + BK <= m0): every strip takes every k-step
+  auto mfmas_full = [&](auto cur_tag) {
+    constexpr int cur = decltype(cur_tag)::value;
     const double *Xs = smem + cur * STAGE;
     const double *Ys = Xs + BK * LDT;
 #pragma unroll
@@ -1328,15 +1423,55 @@ __global__ __launch_bounds__(256, 2) void whiten_synth_kernel(WhitenSynth a, int
 #pragma unroll
       for (int j = 0; j < NJ; ++j) bb[j] = Ys[kr * LDT + wn * NT + j * 16 + fr];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if (k0 + kk * 4 > m0 + (2 * i + wm) * 16 + 15) continue;
+      for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[i], bb[j], acc[i][j], 0, 0, 0);
-      }
     }
+  };
+  // stage ts = 0..7 of the tile row's own 128 k-values, k0 = m0 + 16 ts.  X[k][m] = 0 for k > m: strip t = 2 i + wm (rows
+  // m0 + 16 t .. + 15) sees nothing from k-steps k0 + 4 kk > m0 + 16 t + 15, i.e. it takes all four k-steps of the stage
+  // when t >= ts and none otherwise.  One 32-bit test of uniform values per strip (a scalar compare and branch), the strip
+  // as the outer loop: every accumulator still receives its k-steps in ascending order, so the sums are the same.
+  auto mfmas_tri = [&](auto cur_tag, const int ts) {
+    constexpr int cur = decltype(cur_tag)::value;
+    const double *Xs = smem + cur * STAGE;
+    const double *Ys = Xs + BK * LDT;
+    double bb[BK / 4][NJ];
+#pragma unroll
+    for (int kk = 0; kk < BK / 4; ++kk)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) bb[kk][j] = Ys[(kk * 4 + fq) * LDT + wn * NT + j * 16 + fr];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (2 * i + wm < ts) continue;
+      double av[BK / 4];
+#pragma unroll
+      for (int kk = 0; kk < BK / 4; ++kk) av[kk] = Xs[(kk * 4 + fq) * LDT + (2 * i + wm) * 16 + fr];
+#pragma unroll
+      for (int kk = 0; kk < BK / 4; ++kk)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kk], bb[kk][j], acc[i][j], 0, 0, 0);
+    }
+  };
+  // the 8 tm full stages, unrolled by two (an even count: buffers 0, 1), then the eight triangular stages
+  const int nfull = 8 * tm;
+  for (int s = 0; s < nfull; s += 2) {
+    next(c0_tag{}, s);
+    mfmas_full(c0_tag{});
     __syncthreads();
-    cur ^= 1;
+    next(c1_tag{}, s + 1);
+    mfmas_full(c1_tag{});
+    __syncthreads();
+  }
+  for (int t = 0; t < 8; t += 2) {
+    next(c0_tag{}, nfull + t);
+    mfmas_tri(c0_tag{}, t);
+    __syncthreads();
+    next(c1_tag{}, nfull + t + 1);
+    mfmas_tri(c1_tag{}, t + 1);
+    __syncthreads();
   }
   double *wcol = smem, *red = smem + 128;
   if (tid < BM) wcol[tid] = wreg;
