@@ -435,8 +435,9 @@ int lsqamd_dpdy(lsqamd_fit *fit, const double *gt, int64_t m, void *dev_scratch,
 int64_t lsqamd_nf(const lsqamd_fit *fit);                         /* nchiv (__init__.py:574) */
 
 /* ---- batched fits (SURVEY.md 8a row a8 / BASELINE.json config 5) --------------------
- * B independent fits of ONE shape -- same model, x, data means and diagonal data whitening,
- * different (diagonal) priors and starting points -- advanced in lockstep with all LM state
+ * B independent fits of ONE shape -- same model, x and block structure of the data covariance; per fit: (diagonal) priors,
+ * starting points, data means (lsqamdb_set_data_means) and the values of the whitening weights
+ * (lsqamdb_set_data_weights) -- advanced in lockstep with all LM state
  * on the device and one round of kernels captured in a hipGraph.  Device counterpart of the
  * Python loop of whole fits in lsqfit.empbayes_fit (src/lsqfit/_extras.py:153-174); per fit
  * the driver semantics are those of lsqamd_run.  lsqamdb_set_options accepts options.trs = LSQAMD_TRS_LM, _DOGLEG, _DDOGLEG
@@ -461,6 +462,16 @@ int lsqamdb_set_blocks(lsqamdb_fits *fits, int32_t n_blocks, const int64_t *row0
  * covariance and replace the means (simulated_fit_iter / bootstrapped_fit_iter,
  * src/lsqfit/__init__.py:1391-1469,1548-1642) */
 int lsqamdb_set_data_means(lsqamdb_fits *fits, const double *ymean);
+/* per-fit whitening weights: wdiag[B*N], wt[B*sum_block_sq] (NULL without blocks), DEVICE pointers owned by the caller and
+ * valid until the next call or lsqamdb_destroy; tri[n_blocks] replaces the shared flags (0 where ANY fit's block is not
+ * triangular).  wdiag = NULL returns to the shared weights of lsqamdb_set_data / _set_blocks.  Fit b reads wdiag + b*N and
+ * wt + b*sum_block_sq, laid out as lsqamdb_set_blocks lays one fit's out; row0 / size / modes stay those of
+ * lsqamdb_set_blocks.  Nothing is copied, and a captured round graph is dropped.  Serves data errors that change from
+ * fit to fit: empbayes_fit tuning them (doc/source/overview.rst:1745-1775, doc/source/eg7.py: fitargs(z) returning
+ * gvar(y, y*z)) and bootstrapped_fit_iter(datalist=...) (src/lsqfit/__init__.py:1625-1642), where every copy brings its
+ * own covariance.  lsqamdb_run returns LSQAMD_EINVAL when wt is NULL although cfg.n_blocks > 0, or when an array's device
+ * allocation ends before the last fit's weights (weights made for a smaller batch). */
+int lsqamdb_set_data_weights(lsqamdb_fits *fits, const double *wdiag, const double *wt, const int32_t *tri);
 /* mean[B*P]; prec[B*P] = 1/sdev^2 per fit, or -- cfg.prior_dense -- ONE dense P x P precision shared by
  * all fits (simulated / bootstrap copies differ in their prior means, not in the prior covariance) */
 int lsqamdb_set_priors(lsqamdb_fits *fits, const double *mean, const double *prec);

@@ -119,6 +119,7 @@ PROTOTYPES = {
     'lsqamdb_set_blocks': (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                      C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp]),
     'lsqamdb_set_data_means': (C.c_int, [_vp, _dp]),
+    'lsqamdb_set_data_weights': (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_int32)]),
     'lsqamdb_set_priors': (C.c_int, [_vp, _dp, _vp]),
     'lsqamdb_set_options': (C.c_int, [_vp, C.POINTER(Options)]),
     'lsqamdb_run': (C.c_int, [_vp, _dp, C.POINTER(Summary), C.c_int32]),

@@ -5,8 +5,9 @@ starting points (the inner loop of ``lsqfit.empbayes_fit``, src/lsqfit/_extras.p
 the fits share the model, ``x`` and the data covariance (sdev vector, covariance matrix or
 ``dict(sdev=, blocks=)`` -- whitened exactly as in :class:`lsqfit_amd.Whitening`) and differ in
 their diagonal priors, ``p0`` and -- ``ymean`` of shape (n_fits, N) -- the data means
-(simulated / bootstrap refits, src/lsqfit/__init__.py:1391-1469,1548-1642).  Result arrays
-have a leading batch dimension.
+(simulated / bootstrap refits, src/lsqfit/__init__.py:1391-1469,1548-1642).  With ``per_fit_yerr=`` the VALUES of the data
+covariance are per fit too (one block structure): data errors tuned by ``empbayes_fit`` (doc/source/eg7.py), bootstrap copies
+from a ``datalist`` (src/lsqfit/__init__.py:1625-1642).  Result arrays have a leading batch dimension.
 """
 import ctypes as C
 import time
@@ -21,12 +22,30 @@ from .models import MODEL_IDENTITY, MODEL_TAPE
 
 class BatchedFits:
     def __init__(self, model, x, ymean, ysdev, prior_mean, prior_sdev, device=None, svdcut=1e-12,
-                 whitening=None, n_fits=None, prior_prec=None, prior_logdet=None, rows_permuted=False):
-        """``prior_sdev``: per-fit diagonal priors ([n_fits, P] or broadcastable).  Alternatively
+                 whitening=None, n_fits=None, prior_prec=None, prior_logdet=None, rows_permuted=False, per_fit_yerr=None):
+        """``per_fit_yerr``: ``n_fits`` data errors of ONE block structure, each anything :class:`Whitening` accepts as
+        ``yerr`` (``ysdev`` is then not used; a 2-D array there stays ONE covariance matrix) -- or ``whitening=`` a list of
+        per-fit errors / a :class:`lsqfit_amd.whiten.BatchWhitening`.  The data errors an ``empbayes_fit`` tunes
+        (doc/source/eg7.py) and the copies of ``bootstrapped_fit_iter(datalist=...)`` (src/lsqfit/__init__.py:1625-1642).
+
+        ``prior_sdev``: per-fit diagonal priors ([n_fits, P] or broadcastable).  Alternatively
         ``prior_prec`` (P x P) + ``prior_logdet``: ONE correlated prior covariance shared by all
         fits (its inverse and log-determinant, e.g. from :class:`Whitening`), per-fit means only."""
         import torch
-        from .whiten import Whitening
+        from .whiten import BatchWhitening, Whitening, stack_whitenings
+        if isinstance(whitening, (list, tuple)):
+            per_fit_yerr, whitening = whitening, None
+        if per_fit_yerr is not None and whitening is not None:
+            raise ValueError('give per_fit_yerr or whitening, not both')
+        if per_fit_yerr is not None and not isinstance(per_fit_yerr, BatchWhitening):
+            per_fit_yerr = list(per_fit_yerr)
+            if not per_fit_yerr:
+                raise ValueError('per_fit_yerr must have n_fits entries')
+            for what, arr in (('n_fits', n_fits), ('prior_mean', None if prior_mean is None else len(prior_mean))):
+                if arr is not None and int(arr) != len(per_fit_yerr):
+                    raise ValueError('per_fit_yerr has %d entries, %s says %d fits' % (len(per_fit_yerr), what, int(arr)))
+            if np.ndim(ymean) == 2 and np.shape(ymean)[0] != len(per_fit_yerr):
+                raise ValueError('per_fit_yerr has %d entries, ymean has %d rows' % (len(per_fit_yerr), np.shape(ymean)[0]))
         if not torch.cuda.is_available():
             raise RuntimeError('lsqfit_amd: no MI355X visible; the batched fitter has no CPU path')
         self.lib = lib = _lib.load()
@@ -34,6 +53,11 @@ class BatchedFits:
         ymean = np.ascontiguousarray(ymean, np.float64)
         ymeans = ymean if ymean.ndim == 2 else None
         ymean = ymean[0] if ymean.ndim == 2 else ymean.reshape(-1)
+        if per_fit_yerr is not None:
+            whitening = per_fit_yerr if isinstance(per_fit_yerr, BatchWhitening) else \
+                stack_whitenings(ymean, per_fit_yerr, svdcut=svdcut)
+        self.svdcut = svdcut
+        self._weights = None          # (wdiag, wt) device tensors the library reads in place: alive as long as it may
         if whitening is None:
             yerr = ysdev if isinstance(ysdev, dict) else np.asarray(ysdev, np.float64)
             if not isinstance(yerr, dict) and yerr.ndim < 2:
@@ -48,7 +72,12 @@ class BatchedFits:
                 raise ValueError('identity model with interleaved covariance components: reorder the data')
             x = np.asarray(x, np.float64).reshape(ymean.size, model.n_x)[self._perm]
             ymean = np.ascontiguousarray(ymean[self._perm])
+        batch_wh = whitening if isinstance(whitening, BatchWhitening) else None
+        if batch_wh is not None and n_fits is None and prior_mean is None:
+            n_fits = batch_wh.n_fits
         row0, size, modes, tri, wt = wh.block_arrays()
+        self._row0, self._size, self._modes, self._wperm = row0, size, modes, getattr(wh, 'perm', None)
+        self._shared_wh = wh          # what set_data_weights(None) returns to (a batch made with per-fit weights: fit 0's)
         self.has_prior = prior_mean is not None
         self.prior_dense = prior_prec is not None
         if self.has_prior:
@@ -103,7 +132,7 @@ class BatchedFits:
             consts = np.ascontiguousarray(model.consts, np.float64)
             self._check(lib.lsqamdb_set_tape(h, code.ctypes.data_as(C.POINTER(C.c_int32)), code.size,
                                              _lib.dptr(consts), consts.size), 'set_tape')
-        wd = np.ascontiguousarray(wh.wdiag)
+        wd = np.ascontiguousarray(wh.wdiag if batch_wh is None else wh.wdiag[0])
         self._check(lib.lsqamdb_set_data(h, _lib.dptr(ymean), _lib.dptr(wd)), 'set_data')
         if len(size):
             self._check(lib.lsqamdb_set_blocks(
@@ -112,6 +141,8 @@ class BatchedFits:
                 _lib.anyptr(wt)), 'set_blocks')
         if ymeans is not None:
             self.set_data_means(ymeans)
+        if batch_wh is not None:
+            self.set_data_weights(batch_wh)
         if self.has_prior and self.prior_dense:
             self.set_prior_means(pm)
         elif self.has_prior:
@@ -145,6 +176,45 @@ class BatchedFits:
         if self._perm is not None:
             ymeans = np.ascontiguousarray(ymeans[:, self._perm])
         self._check(self.lib.lsqamdb_set_data_means(self.h, _lib.dptr(ymeans)), 'set_data_means')
+
+    def set_data_weights(self, per_fit_yerr):
+        """New data errors, one per fit (``n_fits`` entries, each anything :class:`Whitening` accepts as ``yerr``, or a
+        :class:`lsqfit_amd.whiten.BatchWhitening`), of the block structure the handle was made for: re-weights between runs
+        without a new handle.  ``None`` returns to the shared weights the handle was made with."""
+        import torch
+        from .whiten import BatchWhitening, stack_whitenings
+        if per_fit_yerr is None:
+            if isinstance(self._shared_wh, BatchWhitening):
+                raise ValueError('set_data_weights(None): this batch was made with per-fit weights, it has no shared ones')
+            self._check(self.lib.lsqamdb_set_data_weights(self.h, None, None, None), 'set_data_weights')
+            self._weights = None
+            self.wh = self._shared_wh
+            return
+        bw = per_fit_yerr if isinstance(per_fit_yerr, BatchWhitening) else \
+            stack_whitenings(np.empty(self.N), list(per_fit_yerr), svdcut=self.svdcut)
+        if bw.n_fits != self.B or bw.n_data != self.N:
+            raise ValueError('set_data_weights: weights for %d fits of %d data, the batch has %d fits of %d'
+                             % (bw.n_fits, bw.n_data, self.B, self.N))
+        same_perm = (bw.perm is None) == (self._wperm is None) and (bw.perm is None or np.array_equal(bw.perm, self._wperm))
+        if not (same_perm and np.array_equal(bw.row0, self._row0) and np.array_equal(bw.size, self._size)):
+            raise ValueError('set_data_weights: another block structure than the one the batch was made for')
+        if not np.array_equal(bw.modes, self._modes):
+            raise ValueError('set_data_weights: svdcut keeps other numbers of modes (%s) than the batch was made for (%s)'
+                             % (list(bw.modes), list(self._modes)))
+        side = _lib.side_stream(self.device)
+        with torch.cuda.stream(side):
+            wd = torch.from_numpy(np.ascontiguousarray(bw.wdiag, np.float64)).to(self.device)
+            wt = None
+            if len(bw.size):
+                wt = bw.wt if isinstance(bw.wt, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(bw.wt)).to(self.device)
+                wt = wt.contiguous()
+        side.synchronize()
+        tri = np.ascontiguousarray(bw.tri, np.int32)
+        self._check(self.lib.lsqamdb_set_data_weights(
+            self.h, C.c_void_p(wd.data_ptr()), C.c_void_p(wt.data_ptr()) if wt is not None else None,
+            tri.ctypes.data_as(C.POINTER(C.c_int32))), 'set_data_weights')
+        self._weights = (wd, wt)
+        self.wh = bw
 
     def set_prior_means(self, mean):
         """Dense shared prior: new per-fit means (the shared precision is re-sent with them)."""

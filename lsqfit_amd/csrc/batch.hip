@@ -5,7 +5,9 @@
 // whole fits (src/lsqfit/_extras.py:153-174, BASELINE.json config 5): the fits share the
 // model, x and the data whitening (1/sdev for the 1x1 rows, W_b per correlated block), and
 // differ in the prior (mean / sdev per fit), the starting point and -- for simulated /
-// bootstrap refits (src/lsqfit/__init__.py:1391-1469,1548-1642) -- the data means.  Per fit the GSL trust/lm/nielsen/scaling/
+// bootstrap refits (src/lsqfit/__init__.py:1391-1469,1548-1642) -- the data means; with lsqamdb_set_data_weights also the VALUES
+// of the whitening weights (the block structure stays shared): data errors tuned by empbayes_fit (doc/source/eg7.py), bootstrap
+// copies from a datalist (src/lsqfit/__init__.py:1625-1642).  Per fit the GSL trust/lm/nielsen/scaling/
 // convergence logic of lm_driver.hip is restated as small per-fit device kernels (b_decide,
 // b_post); the heavy kernels are the same ones the single-fit path uses, launched with a
 // batch dimension: model kernels (grid.y), TN GEMM (grid.z) for J^T J and the Cholesky
@@ -466,6 +468,16 @@ struct lsqamdb_fits {
   // shared inputs
   double *x = nullptr, *ymean = nullptr, *wdiag = nullptr;
   int64_t ymean_stride = 0;  // 0 shared, N per-fit
+  // per-fit whitening weights (lsqamdb_set_data_weights): the caller's device arrays, not copied.  wdiag_b / wt_b are what the
+  // kernels read -- the workspace copies of lsqamdb_set_data / _set_blocks with strides 0, or the caller's with strides N and
+  // sum_block_sq; tri_b likewise (the caller's flags hold for every fit's block)
+  const double *pf_wdiag = nullptr, *pf_wt = nullptr;
+  std::vector<int32_t> pf_tri;
+  const double *wdiag_b() const { return pf_wdiag ? pf_wdiag : wdiag; }
+  const double *wt_b() const { return pf_wdiag ? pf_wt : wt; }
+  int64_t wdiag_stride() const { return pf_wdiag ? N : 0; }
+  int64_t wt_stride() const { return pf_wdiag ? (int64_t)cfg.sum_block_sq : 0; }
+  int32_t tri_b(size_t k) const { return pf_wdiag ? pf_tri[k] : h_tri[k]; }
   // correlated data blocks (shared by the fits)
   uint8_t *in_block = nullptr;
   int64_t *blk_row0 = nullptr, *blk_size = nullptr, *blk_woff = nullptr;
@@ -614,8 +626,8 @@ ModelArgs model_args_b(const lsqamdb_fits *f, const double *p) {
   m.model = f->cfg.model;
   m.n_data = f->N; m.n_param = f->P;
   m.n_x = f->cfg.n_x > 0 ? f->cfg.n_x : 1;
-  m.x = f->x; m.ymean = f->ymean; m.wdiag = f->wdiag;
-  m.ymean_stride = f->ymean_stride;
+  m.x = f->x; m.ymean = f->ymean; m.wdiag = f->wdiag_b();
+  m.ymean_stride = f->ymean_stride; m.wdiag_stride = f->wdiag_stride();
   m.in_block = f->cfg.n_blocks > 0 ? f->in_block : nullptr;
   m.p = p; m.tape = f->tape; m.n_tape = f->n_tape; m.consts = f->consts;
   m.n_batch = f->B; m.p_stride = f->P; m.batch_active = f->s.active;
@@ -647,15 +659,16 @@ int jacobian_all(lsqamdb_fits *f, const int32_t *mask) {
   m.batch_active = mask;
   m.out_stride = N * f->ld;
   HIPCHK(f, launch_jacobian_ex(f->st, m, f->J, f->cfg.n_blocks > 0 ? f->Jraw : nullptr, f->ld));
-  // block rows: J_b <- W_b . Jraw_b for every fit (W shared: X stride 0, batch = fits)
+  // block rows: J_b <- W_b . Jraw_b for every fit (batch = fits; X stride 0 when W is shared, else sum_block_sq -- an odd
+  // stride leaves the 16-byte loads to launch_gemm_tn's alignment test)
   for (size_t k = 0; k < f->h_size.size(); ++k) {
     const int64_t Bk = f->h_size[k];
     GemmTN w;
-    w.X = f->wt + f->h_woff[k]; w.ldx = Bk; w.sx = 0;
+    w.X = f->wt_b() + f->h_woff[k]; w.ldx = Bk; w.sx = f->wt_stride();
     w.Y = f->Jraw + f->h_row0[k] * f->ld; w.ldy = f->ld; w.sy = N * f->ld;
     w.C = f->J + f->h_row0[k] * f->ld; w.ldc = f->ld; w.sc = N * f->ld;
     w.M = Bk; w.N = P + 1; w.K = Bk;
-    w.x_upper_tri = f->h_tri[k];
+    w.x_upper_tri = f->tri_b(k);
     w.batch = (int32_t)f->B; w.batch_active = mask;
     HIPCHK(f, launch_gemm_tn(f->st, w));
   }
@@ -733,8 +746,9 @@ int trial_chi2_all(lsqamdb_fits *f) {
   m.out_stride = N;
   HIPCHK(f, launch_residual_ex(f->st, m, f->r, f->cfg.n_blocks > 0 ? f->r_raw : nullptr));
   if (f->cfg.n_blocks > 0)
-    HIPCHK(f, launch_block_whiten_vec(f->st, f->wt, f->blk_row0, f->blk_size, f->blk_woff, f->cfg.n_blocks,
-                                      f->cfg.max_block, f->r_raw, f->r, (int32_t)B, N, f->s.active));
+    HIPCHK(f, launch_block_whiten_vec(f->st, f->wt_b(), f->blk_row0, f->blk_size, f->blk_woff, f->cfg.n_blocks,
+                                      f->cfg.max_block, f->r_raw, f->r, (int32_t)B, N, f->s.active, INT64_MAX,
+                                      f->wt_stride()));
   hipLaunchKernelGGL(b_sumsq_stage1, dim3((unsigned)f->nrparts, (unsigned)B), dim3(256), 0, f->st, f->r, N, N,
                      f->spart, f->nrparts, f->s.active);
   const bool dense_prior = f->cfg.has_prior && f->cfg.prior_dense;
@@ -828,10 +842,31 @@ int round_trs(lsqamdb_fits *f) {
 int round_any(lsqamdb_fits *f) { return f->opt.trs == LSQAMD_TRS_LM ? round_all(f) : round_trs(f); }
 
 // ---- the stages of lsqamdb_run -------------------------------------------------------------------------------------
+// does the device allocation p points into reach n doubles beyond p?  (what the engine can know of a caller's array: weights
+// made for fewer fits than the handle runs would be read past their end.  Memory the runtime cannot name a range for --
+// a pool's sub-allocation is judged by its segment -- is taken on trust)
+bool holds_doubles(const double *p, int64_t n) {
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)const_cast<double *>(p)) != hipSuccess) {
+    (void)hipGetLastError();
+    return true;
+  }
+  const char *lo = static_cast<const char *>(static_cast<const void *>(base));
+  const char *q = reinterpret_cast<const char *>(p);
+  return q >= lo && (size_t)(q - lo) + sizeof(double) * (size_t)n <= size;
+}
+
 int inputs_ready(lsqamdb_fits *f) {
   if (!f->have_data || (f->cfg.has_prior && !f->have_prior) || (f->cfg.n_blocks > 0 && !f->have_blocks) ||
       (f->cfg.model != LSQAMD_MODEL_IDENTITY && !f->have_x) || (f->cfg.model == LSQAMD_MODEL_TAPE && !f->have_tape))
     FAIL(f, LSQAMD_EINVAL, "run: inputs missing");
+  if (f->pf_wdiag) {   // per-fit weights: the caller's arrays must hold every fit of THIS batch
+    if (f->cfg.n_blocks > 0 && !f->pf_wt) FAIL(f, LSQAMD_EINVAL, "run: per-fit weights without wt, but the config has blocks");
+    if (!holds_doubles(f->pf_wdiag, (int64_t)f->B * f->N) ||
+        (f->cfg.n_blocks > 0 && !holds_doubles(f->pf_wt, (int64_t)f->B * f->cfg.sum_block_sq)))
+      FAIL(f, LSQAMD_EINVAL, "run: the per-fit weights were set for another number of fits (need %d)", (int)f->B);
+  }
   return 0;
 }
 
@@ -870,8 +905,8 @@ int try_one_launch(lsqamdb_fits *f, const double *p0) {
       f->N > lsqamd_jit::fit_row_limit(k, f->cfg.n_blocks != 0) || f->cfg.n_blocks > 64) return 0;
   if (f->opt.maxit < 1 || f->opt.maxit > 20000 || f->opt.trs != LSQAMD_TRS_LM) return 0;
   lsqamd_jit::FitArgs a;
-  a.x = f->x; a.ymean = f->ymean; a.wdiag = f->wdiag; a.n_data = f->N;
-  a.in_block = f->in_block; a.wt = f->wt;
+  a.x = f->x; a.ymean = f->ymean; a.wdiag = f->wdiag_b(); a.n_data = f->N;
+  a.in_block = f->in_block; a.wt = f->wt_b();
   a.blk_row0 = reinterpret_cast<const long long *>(f->blk_row0); a.blk_size = reinterpret_cast<const long long *>(f->blk_size);
   a.blk_woff = reinterpret_cast<const long long *>(f->blk_woff); a.n_blocks = f->cfg.n_blocks;
   a.p0 = f->px; a.p = f->px; a.p_trial = f->pxt; a.dscale = f->diag; a.apk = f->red; a.gvec = f->gvec();
@@ -885,6 +920,7 @@ int try_one_launch(lsqamdb_fits *f, const double *p0) {
   lsqamd_jit::FitBatch bt;
   bt.ymean_stride = f->ymean_stride; bt.prec_stride = f->cfg.prior_dense ? 0 : P; bt.tile_stride = f->red_stride;
   bt.cov_stride = f->m_stride; bt.scratch_stride = f->w_stride;
+  bt.wdiag_stride = f->wdiag_stride(); bt.wt_stride = f->wt_stride();
   bt.logdet = f->logdet; bt.mu = f->s.mu; bt.chi2 = f->s.chi2;
   bt.nit = f->s.nit; bt.info = f->s.info; bt.status = f->s.status; bt.nfev = f->s.nfev; bt.njev = f->s.njev;
   bt.active = f->s.active; bt.reason = f->s.bad;
@@ -1093,6 +1129,23 @@ int lsqamdb_set_data_means(lsqamdb_fits *f, const double *ymean) try {
   if (!f->have_data) FAIL(f, LSQAMD_EINVAL, "set_data_means: call lsqamdb_set_data first");
   HIPCHK(f, copy_sync(f, f->ymean, ymean, sizeof(double) * f->B * f->N, hipMemcpyHostToDevice));
   f->ymean_stride = f->N;
+  return 0;
+} LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
+
+/* per-fit whitening weights: wdiag[B*N], wt[B*sum_block_sq] (NULL without blocks), DEVICE pointers owned by the caller and
+ * valid until the next call or lsqamdb_destroy; tri[n_blocks] replaces the shared flags (0 where ANY fit's block is not
+ * triangular).  wdiag = NULL returns to the shared weights of lsqamdb_set_data / _set_blocks. */
+int lsqamdb_set_data_weights(lsqamdb_fits *f, const double *wdiag, const double *wt, const int32_t *tri) try {
+  if (!f) return LSQAMD_EINVAL;
+  (void)hipStreamSynchronize(f->st);
+  if (f->gexec) { (void)hipGraphExecDestroy(f->gexec); f->gexec = nullptr; }   // (its nodes hold the old pointers)
+  if (f->graph) { (void)hipGraphDestroy(f->graph); f->graph = nullptr; }
+  f->ran = false; f->have_cov = false;
+  f->pf_wdiag = nullptr; f->pf_wt = nullptr; f->pf_tri.clear();
+  if (!wdiag) return 0;
+  if (f->cfg.n_blocks > 0 && !tri) FAIL(f, LSQAMD_EINVAL, "set_data_weights: tri is needed with blocks");
+  f->pf_wdiag = wdiag; f->pf_wt = wt;
+  if (f->cfg.n_blocks > 0) f->pf_tri.assign(tri, tri + f->cfg.n_blocks);
   return 0;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
 

@@ -251,6 +251,7 @@ struct ModelArgs {
   int32_t n_batch = 1;
   int64_t p_stride = 0, out_stride = 0;
   int64_t ymean_stride = 0;  // 0: the fits share ymean; n_data: fit b reads ymean + b*n_data
+  int64_t wdiag_stride = 0;  // 0: the fits share wdiag; n_data: fit b reads wdiag + b*n_data (lsqamdb_set_data_weights)
   const int32_t *batch_active = nullptr;
   // cosine model: device flag "some |w x| may reach the far range of the trig reduction" (launch_trig_range);
   // set: the kernel without far-range code runs unless the flag says otherwise.  null: the safe kernel only
@@ -302,7 +303,8 @@ hipError_t launch_block_whiten_vec(hipStream_t st, const double *wt, const int64
                                    int64_t max_block, const double *delta, double *r_out,
                                    int32_t batch = 1, int64_t stride = 0,
                                    const int32_t *batch_active = nullptr,
-                                   int64_t skip_from = INT64_MAX);  // blocks of >= skip_from rows are left out
+                                   int64_t skip_from = INT64_MAX,   // blocks of >= skip_from rows are left out
+                                   int64_t wt_stride = 0);          // batch entry z reads wt + z*wt_stride (0: shared weights)
 // packed upper tiles <- sum over split-K slabs (matrix layout, P x ld each)
 hipError_t launch_finalize_pack(hipStream_t st, const double *slabs, int32_t splits,
                                 int64_t split_stride, int64_t P, int64_t ld, double *apk,

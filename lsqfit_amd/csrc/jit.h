@@ -14,9 +14,10 @@ struct LaunchArgs {
   const unsigned char *in_block = nullptr;
   double *out_w = nullptr, *out_raw = nullptr;
   int64_t ld = 1, n_data = 0;
-  // batch (blockIdx.y): fit b reads p + b * p_stride, ymean + b * ymean_stride, writes at out + b * out_stride
+  // batch (blockIdx.y): fit b reads p + b * p_stride, ymean + b * ymean_stride, wdiag + b * wdiag_stride, writes at
+  // out + b * out_stride
   int32_t n_batch = 1;
-  int64_t p_stride = 0, out_stride = 0, ymean_stride = 0;
+  int64_t p_stride = 0, out_stride = 0, ymean_stride = 0, wdiag_stride = 0;
   const int *batch_active = nullptr;
 };
 
@@ -91,6 +92,7 @@ hipError_t launch_fit(const Kernel *k, hipStream_t st, const FitArgs &a);
 // of FitArgs are those of fit 0, `host` is DEVICE scratch of scratch_stride >= fit_host_cov(P) + P * P + 32 + P doubles per fit)
 struct FitBatch {
   long long ymean_stride, prec_stride, tile_stride, cov_stride, scratch_stride;
+  long long wdiag_stride, wt_stride;     // per-fit whitening weights (0: shared by the fits)
   double *logdet, *mu, *chi2;
   int *nit, *info, *status, *nfev, *njev, *active, *reason;   // reason: 1 done + covariance, 3 done, 2 irregular
 };

@@ -1052,6 +1052,7 @@ extern "C" __global__ __launch_bounds__(256) void lsqamd_jit_lm(LmArgs a) { lm_f
 // formed), 2 irregular -- the host then runs the lockstep engine.
 struct LmBatch {
   long long ymean_stride, prec_stride, tile_stride, cov_stride, scratch_stride;
+  long long wdiag_stride, wt_stride;     // per-fit whitening weights (0: shared by the fits)
   double *logdet, *mu, *chi2;
   int *nit, *info, *status, *nfev, *njev, *active, *reason;
 };
@@ -1059,6 +1060,8 @@ struct LmBatch {
 extern "C" __global__ __launch_bounds__(256) void lsqamd_jit_lmb(LmArgs a, LmBatch b) {
   const long long fit = blockIdx.x;
   a.ymean += fit * b.ymean_stride;
+  a.wdiag += fit * b.wdiag_stride;
+  if (a.wt) a.wt += fit * b.wt_stride;
   a.p0 += fit * LP; a.p += fit * LP; a.p_trial += fit * LP; a.dscale += fit * LP; a.v_out += fit * LP;
   a.apk += fit * b.tile_stride; a.gvec += fit * b.tile_stride;
   if (a.prior_prec) { a.prior_mean += fit * LP; a.prior_prec += fit * b.prec_stride; }
@@ -1090,7 +1093,7 @@ std::string generate(const Plan &pl, bool batch_only = false) {
   o.s += kDevmath;
   o.s += "\nusing namespace lsqamd;\n";
   o.s += "struct Args { const double *x, *p, *ymean, *wdiag; const unsigned char *in_block; double *out_w, *out_raw; long long ld, n_data;\n"
-         "              long long p_stride, out_stride, ymean_stride; const int *batch_active; };\n";
+         "              long long p_stride, out_stride, ymean_stride, wdiag_stride; const int *batch_active; };\n";
   o.s += "static __device__ __forceinline__ double wsum(double v) {\n"
          "#pragma unroll\n  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);\n  return v;\n}\n";
   // index tables of the non-affine private slots
@@ -1125,6 +1128,7 @@ std::string generate(const Plan &pl, bool batch_only = false) {
     // blockIdx.y = fit of a batch (lockstep fits, chi2 at many points): its parameters, data means and output rows
     o.s += "  if (a.batch_active && !a.batch_active[blockIdx.y]) return;\n";
     o.s += "  a.p += (long long)blockIdx.y * a.p_stride;\n  a.ymean += (long long)blockIdx.y * a.ymean_stride;\n";
+    o.s += "  a.wdiag += (long long)blockIdx.y * a.wdiag_stride;\n";
     o.s += "  a.out_w += (long long)blockIdx.y * a.out_stride;\n  if (a.out_raw) a.out_raw += (long long)blockIdx.y * a.out_stride;\n";
     o.f("  __shared__ double sp[%d];\n", pl.P < 1 ? 1 : pl.P);
     o.f("  for (int i = threadIdx.x; i < %d; i += 256) sp[i] = a.p[i];\n  __syncthreads();\n", pl.P);
@@ -1727,9 +1731,10 @@ const Kernel *compile_tape(const int32_t *code, int n_code, const double *consts
 hipError_t launch(const Kernel *k, hipStream_t st, bool jac, const LaunchArgs &a) {
   if (a.n_data <= 0) return hipSuccess;
   struct { const double *x, *p, *ymean, *wdiag; const unsigned char *in_block; double *out_w, *out_raw; long long ld, n_data;
-           long long p_stride, out_stride, ymean_stride; const int *batch_active; } args =
+           long long p_stride, out_stride, ymean_stride, wdiag_stride; const int *batch_active; } args =
       {a.x, a.p, a.ymean, a.wdiag, a.in_block, a.out_w, a.out_raw, (long long)a.ld, (long long)a.n_data,
-       (long long)a.p_stride, (long long)a.out_stride, (long long)a.ymean_stride, a.batch_active};
+       (long long)a.p_stride, (long long)a.out_stride, (long long)a.ymean_stride, (long long)a.wdiag_stride,
+       a.batch_active};
   size_t sz = sizeof(args);
   void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
   int64_t blocks = k->l.wave_per_row ? (a.n_data + 3) / 4 : (a.n_data + 255) / 256;
@@ -1747,8 +1752,8 @@ int normal_nq(const Kernel *k) {
 hipError_t launch_normal(const Kernel *k, hipStream_t st, const LaunchArgs &a, double *partial, int blocks) {
   if (!k || !k->l.nrm || blocks < 1) return hipErrorInvalidValue;
   struct { const double *x, *p, *ymean, *wdiag; const unsigned char *in_block; double *out_w, *out_raw; long long ld, n_data;
-           long long p_stride, out_stride, ymean_stride; const int *batch_active; } args =
-      {a.x, a.p, a.ymean, a.wdiag, nullptr, partial, nullptr, 1, (long long)a.n_data, 0, 0, 0, nullptr};
+           long long p_stride, out_stride, ymean_stride, wdiag_stride; const int *batch_active; } args =
+      {a.x, a.p, a.ymean, a.wdiag, nullptr, partial, nullptr, 1, (long long)a.n_data, 0, 0, 0, 0, nullptr};
   size_t sz = sizeof(args);
   void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
   return hipModuleLaunchKernel(k->l.nrm, (unsigned)blocks, 1, 1, 256, 1, 1, 0, st, nullptr, cfg);

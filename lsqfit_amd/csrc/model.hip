@@ -46,7 +46,7 @@ struct ModelDev {
   double *out_raw;  // raw destination for rows inside correlated blocks
   int64_t ld;
   int32_t p_in_lds;
-  int64_t p_stride, out_stride, ymean_stride;
+  int64_t p_stride, out_stride, ymean_stride, wdiag_stride;
   const int32_t *batch_active;
   const int32_t *trig_far;
 };
@@ -62,6 +62,7 @@ __global__ __launch_bounds__(256) void sum_model_kernel(ModelDev m) {
   if (m.batch_active && !m.batch_active[blockIdx.y]) return;
   m.p += (int64_t)blockIdx.y * m.p_stride;
   m.ymean += (int64_t)blockIdx.y * m.ymean_stride;
+  m.wdiag += (int64_t)blockIdx.y * m.wdiag_stride;
   m.out_w += (int64_t)blockIdx.y * m.out_stride;
   if (m.out_raw) m.out_raw += (int64_t)blockIdx.y * m.out_stride;
   const double *pp = m.p;
@@ -143,6 +144,7 @@ __global__ __launch_bounds__(256) void identity_model_kernel(ModelDev m) {
   if (m.batch_active && !m.batch_active[blockIdx.y]) return;
   m.p += (int64_t)blockIdx.y * m.p_stride;
   m.ymean += (int64_t)blockIdx.y * m.ymean_stride;
+  m.wdiag += (int64_t)blockIdx.y * m.wdiag_stride;
   m.out_w += (int64_t)blockIdx.y * m.out_stride;
   if (m.out_raw) m.out_raw += (int64_t)blockIdx.y * m.out_stride;
   const bool blk = m.in_block && m.in_block[row];
@@ -168,6 +170,7 @@ __global__ __launch_bounds__(64) void tape_model_kernel(ModelDev m) {
   if (m.batch_active && !m.batch_active[blockIdx.y]) return;
   m.p += (int64_t)blockIdx.y * m.p_stride;
   m.ymean += (int64_t)blockIdx.y * m.ymean_stride;
+  m.wdiag += (int64_t)blockIdx.y * m.wdiag_stride;
   m.out_w += (int64_t)blockIdx.y * m.out_stride;
   if (m.out_raw) m.out_raw += (int64_t)blockIdx.y * m.out_stride;
   const int P = (int)m.n_param;
@@ -655,7 +658,7 @@ static hipError_t launch_model(hipStream_t st, const ModelArgs &a, double *out_w
   m.out_w = out_w; m.out_raw = out_raw; m.ld = ld;
   m.p_in_lds = 0;
   m.p_stride = a.p_stride; m.out_stride = a.out_stride; m.batch_active = a.batch_active;
-  m.ymean_stride = a.ymean_stride;
+  m.ymean_stride = a.ymean_stride; m.wdiag_stride = a.wdiag_stride;
   m.trig_far = a.model == LSQAMD_MODEL_COSMIX ? a.trig_far : nullptr;
   const unsigned nb = (unsigned)(a.n_batch < 1 ? 1 : a.n_batch);
   switch (a.model) {
@@ -693,6 +696,7 @@ static hipError_t launch_model(hipStream_t st, const ModelArgs &a, double *out_w
           if (pg.jit) {
             lsqamd_jit::LaunchArgs la;
             la.n_batch = (int32_t)nb; la.p_stride = a.p_stride; la.out_stride = a.out_stride; la.ymean_stride = a.ymean_stride;
+            la.wdiag_stride = a.wdiag_stride;
             la.batch_active = a.batch_active;
             la.x = a.x + pg.row0 * a.n_x; la.p = a.p; la.ymean = a.ymean + pg.row0; la.wdiag = a.wdiag + pg.row0;
             la.in_block = a.in_block ? a.in_block + pg.row0 : nullptr;
@@ -717,6 +721,7 @@ static hipError_t launch_model(hipStream_t st, const ModelArgs &a, double *out_w
       if (a.jit) {   // the formula compiled at lsqamd_set_tape time (jit.hip); batched fits / many points: blockIdx.y
         lsqamd_jit::LaunchArgs la;
         la.n_batch = (int32_t)nb; la.p_stride = a.p_stride; la.out_stride = a.out_stride; la.ymean_stride = a.ymean_stride;
+            la.wdiag_stride = a.wdiag_stride;
         la.batch_active = a.batch_active;
         la.x = a.x; la.p = a.p; la.ymean = a.ymean; la.wdiag = a.wdiag; la.in_block = a.in_block;
         la.out_w = out_w; la.out_raw = out_raw; la.ld = ld; la.n_data = a.n_data;

@@ -206,7 +206,7 @@ __global__ __launch_bounds__(256) void block_whiten_vec_kernel(const double *wt,
                                                                const int64_t *woff,
                                                                const double *delta, double *r_out,
                                                                int64_t stride, const int32_t *active,
-                                                               int64_t skip_from) {
+                                                               int64_t skip_from, int64_t wt_stride) {
   __shared__ double sh[4][64];
   const int b = blockIdx.y;
   if (active && !active[blockIdx.z]) return;
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(256) void block_whiten_vec_kernel(const double *wt,
   if ((int64_t)blockIdx.x * 64 >= B) return;
   delta += (int64_t)blockIdx.z * stride;
   r_out += (int64_t)blockIdx.z * stride;
-  const double *W = wt + woff[b];
+  const double *W = wt + (int64_t)blockIdx.z * wt_stride + woff[b];
   const int ml = threadIdx.x & 63, jg = threadIdx.x >> 6;
   const int64_t m = (int64_t)blockIdx.x * 64 + ml;
   double a = 0.0;
@@ -230,11 +230,11 @@ hipError_t launch_block_whiten_vec(hipStream_t st, const double *wt, const int64
                                    const int64_t *bsize, const int64_t *woff, int32_t n_blocks,
                                    int64_t max_block, const double *delta, double *r_out,
                                    int32_t batch, int64_t stride, const int32_t *batch_active,
-                                   int64_t skip_from) {
+                                   int64_t skip_from, int64_t wt_stride) {
   if (n_blocks <= 0) return hipSuccess;
   dim3 grid((unsigned)((max_block + 63) / 64), (unsigned)n_blocks, (unsigned)(batch < 1 ? 1 : batch));
   hipLaunchKernelGGL(block_whiten_vec_kernel, grid, dim3(256), 0, st, wt, row0, bsize, woff, delta,
-                     r_out, stride, batch_active, skip_from);
+                     r_out, stride, batch_active, skip_from, wt_stride);
   return hipGetLastError();
 }
 

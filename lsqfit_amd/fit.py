@@ -280,10 +280,11 @@ class nonlinear_fit(object):
         from .resample import simulated_fits
         return simulated_fits(self, n, pexact, add_priornoise, seed, **kw)
 
-    def bootstrapped_fits(self, n, seed=0, **kw):
-        """``bootstrapped_fit_iter`` (src/lsqfit/__init__.py:1548-1642) as one device batch."""
+    def bootstrapped_fits(self, n=None, seed=0, datalist=None, **kw):
+        """``bootstrapped_fit_iter`` (src/lsqfit/__init__.py:1548-1642) as one device batch; ``datalist``: a list of
+        ``(ymean, yerr)`` or ``(x, ymean, yerr)`` data sets, each with its own covariance (:1625-1642)."""
         from .resample import bootstrapped_fits
-        return bootstrapped_fits(self, n, seed, **kw)
+        return bootstrapped_fits(self, n, seed, datalist, **kw)
 
     # -- chi2(p) / pdf(p) at arbitrary points (SURVEY.md 8 f2) -----------------------------------
     def dchi2(self, p):

@@ -246,9 +246,106 @@ def simulated_fits(fit, n, pexact=None, add_priornoise=False, seed=0, **kw):
     return res
 
 
-def bootstrapped_fits(fit, n, seed=0, **kw):
+def _prior_err(wh):
+    """the fit's prior errors as ``nonlinear_fit`` takes them: sdev vector, or the covariance matrix of a correlated prior"""
+    if not wh.prior_dense:
+        return wh.prior_sdev
+    cov = np.diag(np.asarray(wh.prior_sdev, float) ** 2)
+    for k in wh.prior_blocks:
+        cov[np.ix_(k['idx'], k['idx'])] = k['cov']
+    return cov
+
+
+def _datalist_fits(fit, datalist, n, seed, tol=None, maxit=None, covariance=True):
+    """``bootstrapped_fit_iter(datalist=...)`` (src/lsqfit/__init__.py:1625-1642): every entry of ``datalist`` -- ``(ymean, yerr)``
+    or ``(x, ymean, yerr)`` -- is a data set of its own, means AND covariance; the prior means are redrawn around the fit's
+    prior (:1635).  One lockstep batch with per-fit whitening weights when the fit is one the engine runs, every ``x`` is the
+    fit's and the covariances have one block structure; else copy by copy."""
+    from .fit import nonlinear_fit
+    from .whiten import stack_whitenings
+    wh = fit.whitening
+    if getattr(wh, 'joint', False):
+        raise NotImplementedError('bootstrapped_fits(datalist=...) of a fit whose data are correlated with its prior (cross=)')
+    items = []
+    for d in datalist:
+        if n is not None and len(items) >= n:
+            break
+        d = tuple(d)
+        if len(d) not in (2, 3):
+            raise ValueError('datalist entries are (ymean, yerr) or (x, ymean, yerr)')
+        x, ym, ye = d if len(d) == 3 else (None,) + d
+        items.append((x, np.asarray(ym, float).reshape(-1), ye))
+    nc, P = len(items), fit.pmean.size
+    if nc == 0:
+        raise ValueError('bootstrapped_fits: datalist is empty')
+    tol = fit.tol if tol is None else tol
+    maxit = fit.maxit if maxit is None else maxit
+    pm = None
+    if wh.has_prior:
+        rng = np.random.Generator(np.random.PCG64(seed))
+        pm = wh.prior_mean[None, :] + wh.draw_prior(rng, nc)
+    args = getattr(fit, 'fitterargs', {})
+    x0 = np.asarray(fit.problem_x, float) if fit.problem_x is not None and fit.problem_x is not False else None
+    same_x = all(x is None or (x0 is not None and np.shape(x) == x0.shape and np.array_equal(np.asarray(x, float), x0))
+                 for x, _, _ in items)
+    bw = None
+    reg = dict(svdcut=fit.svdcut) if getattr(fit, 'eps', None) is None else dict(svdcut=None, eps=fit.eps)
+    if _batchable(fit) and same_x and 'eps' not in reg and all(ym.size == wh.n_data for _, ym, _ in items):
+        try:
+            bw = stack_whitenings(items[0][1], [ye for _, _, ye in items], svdcut=fit.svdcut)
+        except ValueError:
+            bw = None                 # (structures differ: copy by copy, where each fit says what is wrong with ITS data)
+    ymeans = np.array([ym for _, ym, _ in items]) if all(ym.size == items[0][1].size for _, ym, _ in items) else \
+        [ym for _, ym, _ in items]
+    if bw is not None:
+        dense = wh.has_prior and wh.prior_dense
+        x, ymb = fit.problem_x, ymeans
+        if bw.perm is not None:      # the engine works in the whitening's row order
+            x = np.asarray(x, float).reshape(wh.n_data, fit.model.n_x)[bw.perm]
+            ymb = np.ascontiguousarray(ymeans[:, bw.perm])
+        bf = BatchedFits(fit.model, x, ymb, None, pm, None if (dense or not wh.has_prior) else wh.prior_sdev, whitening=bw,
+                         n_fits=nc, prior_prec=wh.prior_prec if dense else None,
+                         prior_logdet=(wh.logdet - wh.logdet_data) if dense else None, rows_permuted=bw.perm is not None)
+        try:
+            out = bf.run(p0=np.broadcast_to(fit.pmean, (nc, P)), tol=tol, maxit=maxit, covariance=covariance,
+                         scaler=args.get('scaler', 'more'), factor_up=float(args.get('factor_up', 3.0)),
+                         factor_down=float(args.get('factor_down', 2.0)), alg=args.get('alg', 'lm'))
+            if covariance:
+                out['cov'] = bf.cov_all()
+        finally:
+            bf.close()
+        res = ResampledFits(out)
+        res['engine'] = 'batched'
+    else:
+        keys = ('pmean', 'psdev', 'chi2', 'Q', 'nit', 'stopping_criterion', 'logGBF', 'dof')
+        out = {k: [] for k in keys}
+        cov = []
+        perr = _prior_err(wh) if wh.has_prior else None
+        for k, (x, ym, ye) in enumerate(items):
+            f = nonlinear_fit(data=(fit.problem_x if x is None else x, ym, ye), model=fit.model,
+                              prior=(pm[k], perr) if wh.has_prior else None, p0=fit.pmean, tol=tol,
+                              maxit=maxit, fitter=fit.fitter, linear=getattr(fit, 'linear', None) or None, **reg, **args)
+            for key in keys:
+                out[key].append(getattr(f, key))
+            cov.append(f.cov)
+        res = ResampledFits({k: np.array(v) for k, v in out.items()})
+        if covariance:
+            res['cov'] = np.array(cov)
+        res['engine'] = 'sequential (%s)' % fit.fitter
+        res['rounds'] = nc
+    res['ymeans'] = ymeans
+    res['prior_means'] = pm
+    return res
+
+
+def bootstrapped_fits(fit, n=None, seed=0, datalist=None, **kw):
     """n bootstrap copies of ``fit`` refitted from ``p0 = fit.pmean``
-    (``bootstrapped_fit_iter``, __init__.py:1607-1626)."""
+    (``bootstrapped_fit_iter``, __init__.py:1607-1626).  ``datalist``: the copies are the data sets of that list (its first
+    ``n``, or all), each with its own means and covariance (:1625-1642)."""
+    if datalist is not None:
+        return _datalist_fits(fit, datalist, n, seed, **kw)
+    if n is None:
+        raise ValueError('bootstrapped_fits needs n (or a datalist)')
     if getattr(fit.whitening, 'joint', False):
         return _joint_copies(fit, _joint_draws(fit, n, seed, fit.whitening.ymean), fit.pmean, **kw)
     ymeans, pm = bootstrap_data(fit, n, seed)

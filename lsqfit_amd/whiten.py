@@ -513,6 +513,97 @@ class Whitening:
         return diag_rows @ d, diag_rows, [W @ d for W in Wrows], Wrows
 
 
+class BatchWhitening:
+    """The data whitenings of ``n_fits`` data sets of ONE structure (:func:`stack_whitenings`): what
+    ``BatchedFits`` hands to ``lsqamdb_set_data_weights``.  ``wdiag[B, N]``; ``wt[B, sum_block_sq]`` (a CUDA
+    tensor when a device is visible, a numpy array otherwise), fit b's row laid out as ``Whitening.block_arrays``
+    lays one fit's out; ``tri[n_blocks]`` (1 only where EVERY fit's block is triangular), ``modes``, ``row0``, ``size``
+    shared; ``logdet_data[B]``; ``nchiv_data`` and the row permutation ``perm`` shared."""
+
+    def __init__(self, wdiag, wt, row0, size, modes, tri, logdet_data, nchiv_data, perm):
+        self.wdiag, self.wt = wdiag, wt
+        self.row0, self.size, self.modes, self.tri = row0, size, modes, tri
+        self.logdet_data, self.nchiv_data, self.perm = logdet_data, nchiv_data, perm
+        self.n_fits, self.n_data = wdiag.shape
+
+    def block_arrays(self):
+        """(row0, size, modes, tri, fit 0's wt): the shared structure, as ``Whitening.block_arrays`` returns it."""
+        return self.row0, self.size, self.modes, self.tri, self.wt[0]
+
+
+def stack_whitenings(ymeans, yerrs, svdcut=1e-12, engine=None):
+    """The whitening weights of B data sets whose covariances have ONE block structure -- the data errors an
+    ``empbayes_fit`` tunes (doc/source/overview.rst:1745-1775, doc/source/eg7.py) or the entries of
+    ``bootstrapped_fit_iter(datalist=...)`` (src/lsqfit/__init__.py:1625-1642) -- with ONE :func:`regulate_blocks` call
+    over all B * n_blocks blocks.  ``yerrs``: B entries, each anything :class:`Whitening` accepts as ``yerr``;
+    ``ymeans``: [N] or [B, N] (only its row count is used: the weights do not depend on the means).  Fit b's numbers are
+    those of ``Whitening(ymean_b, yerrs[b], svdcut=svdcut, engine=engine)``.  ValueError, naming the first offending fit,
+    when a fit's block structure (row permutation, first rows, sizes) or its kept modes per block differ from fit 0's."""
+    N = np.asarray(ymeans).shape[-1]
+    B = len(yerrs)
+    if B < 1:
+        raise ValueError('stack_whitenings needs at least one data set')
+    sds, blocks, perm = [], [], None
+    for b, err in enumerate(yerrs):
+        try:
+            sd, blk, pm = _as_blocks(err, N)
+        except ValueError as e:
+            raise ValueError('fit %d: %s' % (b, e)) from None
+        if sd.size != N:
+            raise ValueError('fit %d: %d standard deviations for %d data' % (b, sd.size, N))
+        blk = sorted(blk, key=lambda k: k[0])
+        if b == 0:
+            perm = pm
+        else:
+            same = ((pm is None) == (perm is None) and (pm is None or np.array_equal(pm, perm)) and
+                    [(r0, c.shape[0]) for r0, c in blk] == [(r0, c.shape[0]) for r0, c in blocks[0]])
+            if not same:
+                raise ValueError('fit %d: the block structure of its data covariance differs from fit 0\'s' % b)
+        sds.append(sd)
+        blocks.append(blk)
+    nblk = len(blocks[0])
+    row0 = np.array([r0 for r0, _ in blocks[0]], np.int64)
+    size = np.array([c.shape[0] for _, c in blocks[0]], np.int64)
+    regs = regulate_blocks([c for blk in blocks for _, c in blk], svdcut, engine=engine)
+    in_block = np.zeros(N, bool)
+    for r0, n in zip(row0, size):
+        in_block[r0:r0 + n] = True
+    d = ~in_block
+    wdiag = np.ones((B, N))
+    logdet = np.zeros(B)
+    modes = np.array([k['modes'] for k in regs[:nblk]], np.int64)
+    tri = np.ones(nblk, np.int32)
+    for b in range(B):
+        mine = regs[b * nblk:(b + 1) * nblk]
+        if [k['modes'] for k in mine] != list(modes):
+            raise ValueError('fit %d: svdcut keeps other numbers of modes in its blocks (%s) than in fit 0\'s (%s)'
+                             % (b, [k['modes'] for k in mine], list(modes)))
+        ld = 0.0
+        for j, k in enumerate(mine):             # (summed in Whitening's order: the same bits)
+            ld += k['logdet']
+            tri[j] &= int(k['tri'])
+        if np.any(sds[b][d] <= 0) or not np.all(np.isfinite(sds[b][d])):
+            raise ValueError('fit %d: some input data have zero or non-finite standard deviations' % b)
+        wdiag[b, d] = 1.0 / sds[b][d]
+        logdet[b] = ld + 2.0 * float(np.sum(np.log(sds[b][d])))
+    nchiv = int(np.sum(d)) + int(np.sum(modes))
+    ssq = int(np.sum(size * size))
+    if nblk and any('Wt_dev' in k for k in regs):
+        import torch                              # weights made on the device stay there; the others join them
+        from . import _lib
+        dev = next(k['Wt_dev'].device for k in regs if 'Wt_dev' in k)
+        side = _lib.side_stream(dev)
+        with torch.cuda.stream(side):
+            wt = torch.cat([k['Wt_dev'].reshape(-1) if 'Wt_dev' in k else
+                            torch.from_numpy(np.ascontiguousarray(k['Wt'], np.float64).reshape(-1)).to(dev)
+                            for k in regs]).reshape(B, ssq).contiguous()
+        side.synchronize()
+    else:
+        wt = np.ascontiguousarray(np.concatenate([k['Wt'].reshape(-1) for k in regs]).reshape(B, ssq)
+                                  if nblk else np.zeros((B, 0)), np.float64)
+    return BatchWhitening(wdiag, wt, row0, size, modes, tri, logdet, nchiv, perm)
+
+
 def _components(cov):
     """Connected components of the off-diagonal pattern of a symmetric matrix, each sorted, ordered
     by their first index (gvar.evalcov_blocks)."""
