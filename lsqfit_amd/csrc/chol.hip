@@ -11,7 +11,8 @@
 //   diagonal block   factor + triangular inverse by one workgroup: potf2_mfma.hip (tiles
 //                    resident in the MFMA accumulator layout; default) or the LDS-resident
 //                    kernel below (LSQAMD_POTF2=lds)
-//   row panel        U[k, k+nb:] = inv(U_kk)^T A[k, k+nb:]          (in-place TN GEMM, 128 x 64 tiles)
+//   row panel        U[k, k+nb:] = inv(U_kk)^T A[k, k+nb:]          (in-place TN GEMM, 128 x 64 tiles; between
+//                    two fused launches one-shot, with the update of diagonal block k + 2 riding along)
 //   trailing update  A[k+nb:, k+nb:] -= U[k, k+nb:]^T U[k, k+nb:]    (TN GEMM, upper tiles; while it
 //                    is large, one launch with the next diagonal block: trail_potf2_kernel)
 // Extra columns to the right of the n x n block ride along in the row panels, so
@@ -32,7 +33,7 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 
 size_t potrf_work_bytes(int64_t n) {
   const int64_t nblk = (n + NB - 1) / NB;
-  return (size_t)nblk * NB * NB * sizeof(double);
+  return (size_t)(nblk + 1) * NB * NB * sizeof(double);   // + potrf_upper's scratch tile
 }
 
 __device__ __forceinline__ double readlane_d(double v, int lane) {
@@ -389,7 +390,7 @@ static hipError_t launch_potf2(hipStream_t st, double *A, int64_t lda, int nb, d
 
 hipError_t potrf_upper_batched(hipStream_t st, double *A, int64_t n, int64_t lda, int64_t n_cols,
                                double *work, int32_t *dev_info, int32_t batch, int64_t strideA,
-                               int64_t strideW, const int32_t *active, bool info_zeroed) {
+                               int64_t strideW, const int32_t *active, bool info_zeroed, bool work_has_scratch) {
   hipError_t e = info_zeroed ? hipSuccess : hipMemsetAsync(dev_info, 0, sizeof(int32_t) * (size_t)batch, st);
   if (e != hipSuccess) return e;
   // single matrix, everything tile-aligned: the trailing update of step k carries the diagonal
@@ -400,6 +401,24 @@ hipError_t potrf_upper_batched(hipStream_t st, double *A, int64_t n, int64_t lda
   const bool can_fuse = batch == 1 && !active && fuse_min_tiles >= 0 && trail_potf2_available() && (n % NB) == 0 &&
                         (n_cols % NB) == 0 &&
                         !(lda & 1) && !(reinterpret_cast<uintptr_t>(A) & 15);
+  // Between two fused launches the row panel's launch also updates the diagonal block after the next one
+  // (launch_panel_oneshot_diag), from a copy of the unsolved panel tile that the previous fused launch left in
+  // the scratch tile behind the inverses; workgroup 0 of the fused launch then only factors.
+  // LSQAMD_DIAG_IN_PANEL=0 (read per call: developer knob) keeps the update in that workgroup.
+  // Only while workgroup 0 is what the fused launch waits for: at P = 4096 that is from 231 trailing tiles down
+  // (fused launch 36 -> 25-29 us, panel 6.5 -> 10 us); with 253 tiles and more the tile workgroups take 39 us and
+  // longer, the fused launch stays as long as it was and the panel's 3.5 us are a loss
+  // (profiles/potrf_diag_in_panel.txt).  LSQAMD_DIAG_IN_PANEL_MAX_TILES moves the limit.
+  const char *dip_env = getenv("LSQAMD_DIAG_IN_PANEL");
+  const char *dip_max_env = getenv("LSQAMD_DIAG_IN_PANEL_MAX_TILES");
+  const int64_t dip_max_tiles = dip_max_env ? atoll(dip_max_env) : (int64_t)240;
+  const bool diag_in_panel = can_fuse && work_has_scratch && !(dip_env && dip_env[0] == '0') &&
+                             panel_oneshot_diag_available() && !(reinterpret_cast<uintptr_t>(work) & 15);
+  double *pristine = work + ((n + NB - 1) / NB) * NB * NB;
+  auto fused_at = [&](int64_t k) {   // the step at column k ends in a fused launch whose workgroup 0 is relieved
+    const int64_t mb = (n - (k + NB)) / NB;
+    return can_fuse && mb > 0 && mb * (mb + 1) / 2 >= fuse_min_tiles && mb * (mb + 1) / 2 <= dip_max_tiles;
+  };
   bool diag_done = false;  // the diagonal block of this step was factored by the previous launch
   for (int64_t k0 = 0; k0 < n; k0 += NB) {
     const int nb = (int)((n - k0) < NB ? (n - k0) : NB);
@@ -409,6 +428,7 @@ hipError_t potrf_upper_batched(hipStream_t st, double *A, int64_t n, int64_t lda
                        active);
       if (e != hipSuccess) return e;
     }
+    const bool next_in_panel = diag_in_panel && diag_done && fused_at(k0);   // (diag_done: the scratch tile is this step's)
     diag_done = false;
     const int64_t rest = n_cols - (k0 + nb);
     if (rest <= 0) continue;
@@ -419,14 +439,16 @@ hipError_t potrf_upper_batched(hipStream_t st, double *A, int64_t n, int64_t lda
     p.M = nb; p.N = rest; p.K = nb;
     p.x_upper_tri = 1;
     p.batch = batch; p.batch_active = active;
-    e = launch_gemm_tn(st, p);
+    if (next_in_panel) e = launch_panel_oneshot_diag(st, uinv, p.C, lda, rest, pristine, A + (k0 + nb) * lda + (k0 + nb));
+    else e = launch_gemm_tn(st, p);
     if (e != hipSuccess) return e;
     const int64_t mrest = n - (k0 + nb);
     if (mrest <= 0) continue;
     const int64_t tiles = (mrest / NB) * (mrest / NB + 1) / 2;
     if (can_fuse && tiles >= fuse_min_tiles) {
       e = launch_trail_potf2(st, p.C, A + (k0 + nb) * lda + (k0 + nb), lda, mrest, rest, NB,
-                             work + ((k0 + nb) / NB) * NB * NB, dev_info, (int32_t)(k0 + nb));
+                             work + ((k0 + nb) / NB) * NB * NB, dev_info, (int32_t)(k0 + nb),
+                             (diag_in_panel && fused_at(k0 + nb)) ? pristine : nullptr, next_in_panel);
       if (e != hipSuccess) return e;
       diag_done = true;
       continue;
@@ -447,7 +469,7 @@ hipError_t potrf_upper_batched(hipStream_t st, double *A, int64_t n, int64_t lda
 
 hipError_t potrf_upper(hipStream_t st, double *A, int64_t n, int64_t lda, int64_t n_cols,
                        double *work, int32_t *dev_info, bool info_zeroed) {
-  return potrf_upper_batched(st, A, n, lda, n_cols, work, dev_info, 1, 0, 0, nullptr, info_zeroed);
+  return potrf_upper_batched(st, A, n, lda, n_cols, work, dev_info, 1, 0, 0, nullptr, info_zeroed, true);
 }
 
 // ---- back substitution U v = y ------------------------------------------------------

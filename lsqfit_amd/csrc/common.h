@@ -182,7 +182,8 @@ hipError_t launch_wait_counter(hipStream_t st, const int32_t *ctr, int32_t expec
 
 // ---- Cholesky family (chol.hip) ---------------------------------------------------
 constexpr int CHOL_NB = 128;
-// workspace: inverses of the diagonal blocks, ceil(n/NB) * NB*NB doubles
+// workspace: inverses of the diagonal blocks, ceil(n/NB) * NB*NB doubles, and one more NB x NB tile behind
+// them (potrf_upper: the unsolved copy of the next panel tile, see launch_panel_oneshot_diag)
 size_t potrf_work_bytes(int64_t n);
 // In-place upper Cholesky A = U^T U of the leading n x n block of A[n x n_cols]
 // (row-major, lda); columns n..n_cols-1 are carried along (they become U^-T * A[:, n:]).
@@ -193,9 +194,22 @@ hipError_t potrf_upper(hipStream_t st, double *A, int64_t n, int64_t lda, int64_
 // batched: matrix b at A + b*strideA, block inverses at work + b*strideW, info[b];
 // trailing update C -= P^T P (upper tiles; P = 128 x rest panel, C = mrest x rest, both multiples of
 // 128, 16-byte aligned rows) fused with the diagonal block of the next step (= tile (0, 0) of C)
+// pristine_out (or null): tile (0, 1) of C is stored a second time there (128 x 128, row-major) -- the next
+// step's panel launch updates the diagonal block after this one from it.  diag_updated: tile (0, 0) of C
+// carries this step's update already (launch_panel_oneshot_diag did it): workgroup 0 only factors it.
 bool trail_potf2_available();
 hipError_t launch_trail_potf2(hipStream_t st, const double *P, double *C, int64_t lda, int64_t mrest,
-                              int64_t rest, int nb_next, double *uinv_next, int32_t *info, int32_t k0_next);
+                              int64_t rest, int nb_next, double *uinv_next, int32_t *info, int32_t k0_next,
+                              double *pristine_out = nullptr, bool diag_updated = false);
+// The 16 x 16 blocks (ti, tj) of the next diagonal block whose update chain starts from zero with A added
+// after it (the pivot wave's share in the fused launch); every other block's chain starts from A.
+constexpr bool potf2_diag_helper_block(int ti, int tj) { return (tj == 6 && ti < 4) || (tj == 5 && ti < 5); }
+// one-shot row panel U[k, k+1:] = inv(U_kk)^T A[k, k+1:] (128 rows, rest columns, a multiple of 16; 16-byte
+// aligned rows) whose first workgroups apply A[k+1, k+1] -= U[k, k+1]^T U[k, k+1] to Dnext (lda), from
+// `pristine`, the copy of A[k, k+1] that a fused launch left (gemm_tn_f64.hip)
+bool panel_oneshot_diag_available();
+hipError_t launch_panel_oneshot_diag(hipStream_t st, const double *uinv, double *panel, int64_t lda, int64_t rest,
+                                     const double *pristine, double *Dnext);
 // diagonal block (nb <= 128) of the blocked Cholesky: A_kk -> U_kk in place, inv(U_kk) -> uinv
 // (128 x 128, row-major); one workgroup per batch entry (potf2_mfma.hip)
 hipError_t launch_potf2_mfma(hipStream_t st, double *A, int64_t lda, int nb, double *uinv, int32_t *info,
@@ -203,9 +217,12 @@ hipError_t launch_potf2_mfma(hipStream_t st, double *A, int64_t lda, int nb, dou
                              const int32_t *active);
 
 // entries with active[b] == 0 (if given) are skipped
+// work_has_scratch: work holds potrf_work_bytes(n), scratch tile included (potrf_upper; batched callers carve
+// the inverses only)
 hipError_t potrf_upper_batched(hipStream_t st, double *A, int64_t n, int64_t lda, int64_t n_cols,
                                double *work, int32_t *dev_info, int32_t batch, int64_t strideA,
-                               int64_t strideW, const int32_t *active, bool info_zeroed = false);
+                               int64_t strideW, const int32_t *active, bool info_zeroed = false,
+                               bool work_has_scratch = false);
 hipError_t backsolve_upper_batched(hipStream_t st, const double *A, int64_t n, int64_t lda,
                                    const double *work, double *y_inout, int32_t batch, int64_t strideA,
                                    int64_t strideW, int64_t strideY, const int32_t *active,

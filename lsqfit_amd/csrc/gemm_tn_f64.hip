@@ -782,35 +782,37 @@ constexpr size_t GEMM_LDS_BYTES_P = 2 * STAGE_P * sizeof(double);
 constexpr int OS_LDX = 136, OS_PN = 16;
 constexpr size_t GEMM_LDS_BYTES_OS = (size_t)(128 * OS_LDX + 128 * OS_PN) * sizeof(double);
 
-__global__ __launch_bounds__(256) void gemm_tn_f64_panel_oneshot_kernel(GemmDev g) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
+// X: row k = 1 KiB = one wave-instruction (lane -> 2 doubles); 32 rows per wave.  (Leaving the lanes
+// left of the diagonal block out of the request -- half the bytes -- was measured: no gain.)
+__device__ __forceinline__ void oneshot_stage_x(const double *X, int64_t ldx, double *Xs, int wave, int lane) {
   typedef __attribute__((address_space(3))) void lds_void;
   typedef const __attribute__((address_space(1))) void glb_void;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t b = blockIdx.z;
-  if (g.batch_active && !g.batch_active[b]) return;
-  const double *X = g.X + b * g.sx;
-  const int64_t n0 = (int64_t)blockIdx.x * OS_PN;
-  double *Yg = g.C + b * g.sc + n0;              // C aliases Y
-  double *Xs = smem, *Ys = smem + 128 * OS_LDX;
-  // X: row k = 1 KiB = one wave-instruction (lane -> 2 doubles); 32 rows per wave.  (Leaving the lanes
-  // left of the diagonal block out of the request -- half the bytes -- was measured: no gain.)
 #pragma unroll 8
   for (int i = 0; i < 32; ++i) {
     const int k = wave * 32 + i;
-    __builtin_amdgcn_global_load_lds((glb_void *)(X + (int64_t)k * g.ldx + 2 * lane), (lds_void *)(Xs + k * OS_LDX), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((glb_void *)(X + (int64_t)k * ldx + 2 * lane), (lds_void *)(Xs + k * OS_LDX), 16, 0, 0);
   }
-  // Y: 8 rows of 16 doubles per wave-instruction (lane -> row lane / 8, doubles 2 (lane % 8) ..)
+}
+
+// Y: 8 rows of 16 doubles per wave-instruction (lane -> row lane / 8, doubles 2 (lane % 8) ..)
+__device__ __forceinline__ void oneshot_stage_y(const double *Yg, int64_t ldy, double *Ys, int wave, int lane) {
+  typedef __attribute__((address_space(3))) void lds_void;
+  typedef const __attribute__((address_space(1))) void glb_void;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int k8 = (wave * 4 + i) * 8;
-    __builtin_amdgcn_global_load_lds((glb_void *)(Yg + (int64_t)(k8 + (lane >> 3)) * g.ldc + 2 * (lane & 7)),
+    __builtin_amdgcn_global_load_lds((glb_void *)(Yg + (int64_t)(k8 + (lane >> 3)) * ldy + 2 * (lane & 7)),
                                      (lds_void *)(Ys + k8 * OS_PN), 16, 0, 0);
   }
-  __syncthreads();   // (s_waitcnt vmcnt(0) is part of it)
+}
+
+// this wave's two 16-row blocks (wave, 7 - wave) of inv(U_kk)^T Y: acc[r] <-> row 16 i + 4 r + lane / 16, column lane % 16
+__device__ __forceinline__ void oneshot_product(const double *Xs, const double *Ys, int wave, int lane, v4d &acc0,
+                                                v4d &acc1) {
   const int col = lane & 15, q = lane >> 4;
-  const int i0 = wave, i1 = 7 - wave;            // this wave's two 16-row blocks of the output
-  v4d acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+  const int i0 = wave, i1 = 7 - wave;
+  acc0 = (v4d){0.0, 0.0, 0.0, 0.0};
+  acc1 = (v4d){0.0, 0.0, 0.0, 0.0};
   const int n0c = 4 * (i0 + 1), n1c = 4 * (i1 + 1);
 #pragma unroll 4
   for (int kc = 0; kc < n1c; ++kc) {
@@ -822,11 +824,152 @@ __global__ __launch_bounds__(256) void gemm_tn_f64_panel_oneshot_kernel(GemmDev 
       acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, bb, acc0, 0, 0, 0);
     }
   }
+}
+
+// one workgroup: 16 operand columns Yg[0..127][0..15] solved in place
+__device__ __forceinline__ void oneshot_slice(const double *X, int64_t ldx, double *Yg, int64_t ldc, double *smem,
+                                              int tid) {
+  const int lane = tid & 63, wave = tid >> 6;
+  double *Xs = smem, *Ys = smem + 128 * OS_LDX;
+  oneshot_stage_x(X, ldx, Xs, wave, lane);
+  oneshot_stage_y(Yg, ldc, Ys, wave, lane);
+  __syncthreads();   // (s_waitcnt vmcnt(0) is part of it)
+  const int col = lane & 15, q = lane >> 4;
+  const int i0 = wave, i1 = 7 - wave;            // this wave's two 16-row blocks of the output
+  v4d acc0, acc1;
+  oneshot_product(Xs, Ys, wave, lane, acc0, acc1);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    Yg[(int64_t)(16 * i0 + 4 * r + q) * g.ldc + col] = acc0[r];
-    Yg[(int64_t)(16 * i1 + 4 * r + q) * g.ldc + col] = acc1[r];
+    Yg[(int64_t)(16 * i0 + 4 * r + q) * ldc + col] = acc0[r];
+    Yg[(int64_t)(16 * i1 + 4 * r + q) * ldc + col] = acc1[r];
   }
+}
+
+__global__ __launch_bounds__(256) void gemm_tn_f64_panel_oneshot_kernel(GemmDev g) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int64_t b = blockIdx.z;
+  if (g.batch_active && !g.batch_active[b]) return;
+  oneshot_slice(g.X + b * g.sx, g.ldx, g.C + b * g.sc + (int64_t)blockIdx.x * OS_PN, g.ldc, smem, threadIdx.x);   // C aliases Y
+}
+
+// ---- one-shot row panel of step k with the update of the next diagonal block riding along ------
+// A[k+1, k+1] -= U[k, k+1]^T U[k, k+1] needs inv(U_kk) and the unsolved tile A[k, k+1] only, and both
+// exist before this launch.  The first PD_PAIRS workgroups take one pair ti <= tj of 16-column blocks
+// of tile k + 1 each: they solve slices tj and ti of a copy of A[k, k+1] that no panel workgroup
+// overwrites (`pristine`, 128 x 128, row-major) with the panel's own product -- same operands, same
+// order, the bits of the stored panel -- and wave 0 runs the 32-chunk chain of block (ti, tj) on
+// them, exactly as the fused launch's workgroup 0 did (potf2_mfma.hip: diag_update_from_panel4, or
+// diag_update_help4 + diag_update_collect4 for the nine helper blocks).  Redundant flops instead of
+// a hand-off: no workgroup waits for another, the kernel boundary publishes the block.
+// The other workgroups are the panel (oneshot_slice).
+constexpr int PD_PAIRS = 36;
+
+struct PanelDiagArgs {
+  const double *X;          // inv(U_kk), 128 x 128, row-major
+  double *Y;                // A[k, k+1 ..]: rest columns, solved in place
+  int64_t ldc;
+  const double *pristine;   // A[k, k+1] before the solve
+  double *D;                // A[k+1, k+1] (ldc)
+};
+
+__global__ __launch_bounds__(256) void gemm_tn_f64_panel_oneshot_diag_kernel(PanelDiagArgs g) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if (blockIdx.x >= PD_PAIRS) {
+    oneshot_slice(g.X, CHOL_NB, g.Y + (int64_t)(blockIdx.x - PD_PAIRS) * OS_PN, g.ldc, smem, tid);
+    return;
+  }
+  int ti = (int)blockIdx.x, tj = 0;     // pairs column by column: (0,0) (0,1) (1,1) (0,2) ...
+  while (ti > tj) {
+    ti -= tj + 1;
+    ++tj;
+  }
+  const int col = lane & 15, q = lane >> 4;
+  double *Xs = smem, *Ys = smem + 128 * OS_LDX;
+  oneshot_stage_x(g.X, CHOL_NB, Xs, wave, lane);
+  oneshot_stage_y(g.pristine + 16 * tj, CHOL_NB, Ys, wave, lane);
+  v2d y2[4];                            // slice ti waits in registers for its turn in Ys (same lane mapping as the DMA)
+  if (ti != tj) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int k8 = (wave * 4 + i) * 8;
+      y2[i] = *reinterpret_cast<const v2d *>(g.pristine + (int64_t)(k8 + (lane >> 3)) * CHOL_NB + 16 * ti + 2 * (lane & 7));
+    }
+  }
+  v4d c = {0.0, 0.0, 0.0, 0.0};
+  if (wave == 0) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) c[r] = g.D[(int64_t)(16 * ti + 4 * r + q) * g.ldc + 16 * tj + col];
+  }
+  __syncthreads();
+  const int i0 = wave, i1 = 7 - wave;
+  v4d acc0, acc1;
+  double a[32], b[32];                  // wave 0: -u_ti and u_tj, k-chunk kc = rows 4 kc + q of the panel
+  auto solved_to_lds = [&]() {          // the solved slice replaces the operand: the chain's one LDS hop
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      Ys[(16 * i0 + 4 * r + q) * OS_PN + col] = acc0[r];
+      Ys[(16 * i1 + 4 * r + q) * OS_PN + col] = acc1[r];
+    }
+    __syncthreads();
+  };
+  oneshot_product(Xs, Ys, wave, lane, acc0, acc1);
+  solved_to_lds();
+  if (wave == 0) {
+#pragma unroll
+    for (int kc = 0; kc < 32; ++kc) b[kc] = Ys[(4 * kc + q) * OS_PN + col];
+  }
+  if (ti != tj) {                       // (uniform over the workgroup)
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int k8 = (wave * 4 + i) * 8;
+      *reinterpret_cast<v2d *>(Ys + (k8 + (lane >> 3)) * OS_PN + 2 * (lane & 7)) = y2[i];
+    }
+    __syncthreads();
+    oneshot_product(Xs, Ys, wave, lane, acc0, acc1);
+    solved_to_lds();
+    if (wave == 0) {
+#pragma unroll
+      for (int kc = 0; kc < 32; ++kc) a[kc] = -Ys[(4 * kc + q) * OS_PN + col];
+    }
+  } else if (wave == 0) {
+#pragma unroll
+    for (int kc = 0; kc < 32; ++kc) a[kc] = -b[kc];
+  }
+  if (wave != 0) return;
+  const bool helper = potf2_diag_helper_block(ti, tj);   // chain from zero, A added after it
+  v4d acc = helper ? (v4d){0.0, 0.0, 0.0, 0.0} : c;
+#pragma unroll
+  for (int kc = 0; kc < 32; ++kc) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kc], b[kc], acc, 0, 0, 0);
+  if (helper) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] = c[r] + acc[r];
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) g.D[(int64_t)(16 * ti + 4 * r + q) * g.ldc + 16 * tj + col] = acc[r];
+}
+
+bool panel_oneshot_diag_available() {
+  static const bool ok = [] { const char *e = getenv("LSQAMD_PANEL_PN"); return !(e && atoi(e) != 0); }();
+  return ok;
+}
+
+hipError_t launch_panel_oneshot_diag(hipStream_t st, const double *uinv, double *panel, int64_t lda, int64_t rest,
+                                     const double *pristine, double *Dnext) {
+  static PerDeviceOnce attr;
+  const hipError_t ea = attr.run([] {
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_tn_f64_panel_oneshot_diag_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEMM_LDS_BYTES_OS);
+  });
+  if (ea != hipSuccess) return ea;
+  PanelDiagArgs g;
+  g.X = uinv; g.Y = panel; g.ldc = lda; g.pristine = pristine; g.D = Dnext;
+  hipLaunchKernelGGL(gemm_tn_f64_panel_oneshot_diag_kernel, dim3((unsigned)(PD_PAIRS + rest / OS_PN)), dim3(256),
+                     GEMM_LDS_BYTES_OS, st, g);
+  return hipGetLastError();
 }
 
 template <bool VEC, int PNW>

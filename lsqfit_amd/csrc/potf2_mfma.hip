@@ -957,6 +957,8 @@ struct TrailArgs {
   int64_t lda;
   int32_t tiles_m, tiles_n;   // mrest / 128, rest / 128
   int32_t halves;             // tiles are done as two 64-column halves by two workgroups
+  int32_t diag_updated;       // tile (0, 0) carries this step's update already (the panel launch did it)
+  double *pristine;           // (or null) second copy of tile (0, 1) as this launch leaves it: 128 x 128, row-major
 };
 
 constexpr int TBK = 16, TLD = 128 + 16, TSTAGE = 2 * TBK * TLD;
@@ -1029,6 +1031,13 @@ __device__ __forceinline__ void trail_tile(const TrailArgs &t, int tm, int tn, i
 #pragma unroll
       for (int r = 0; r < 4; ++r)
         t.C[(m0 + wm * 64 + i * 16 + fq + 4 * r) * t.lda + n0 + cw + j * 16 + fr] = cv[j][r] - acc[i][j][r];
+    if (t.pristine && tm == 0 && tn == 1) {   // the next step's panel tile, kept unsolved for its diagonal-update workgroups
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          t.pristine[(wm * 64 + i * 16 + fq + 4 * r) * NB + cw + j * 16 + fr] = cv[j][r] - acc[i][j][r];
+    }
   }
 }
 
@@ -1046,6 +1055,10 @@ constexpr int DLD4 = 128 + 8;
 constexpr int DIAG4_HELP_OFF = 128 * DLD4;
 constexpr size_t DIAG4_LDS_BYTES = (size_t)(128 * DLD4 + 9 * 4 * 64) * sizeof(double);
 constexpr int v4_help_skip(int U) { return U == 1 ? 4 : (U == 2 ? 5 : 0); }   // leading tiles of slot 2 done by the pivot wave
+// the panel launch's diagonal-update workgroups (gemm_tn_f64.hip) reproduce this split block by block
+static_assert(potf2_diag_helper_block(3, 6) && !potf2_diag_helper_block(4, 6) && potf2_diag_helper_block(4, 5) &&
+              !potf2_diag_helper_block(5, 5) && !potf2_diag_helper_block(0, 7) && v4_help_skip(1) == 4 && v4_help_skip(2) == 5,
+              "potf2_diag_helper_block (common.h) names the pivot wave's helper tiles");
 
 template <int U>
 __device__ __forceinline__ void diag_update_from_panel4(TileRegs4 &T, const double *Ps, int lane) {
@@ -1174,6 +1187,10 @@ __global__ __launch_bounds__(256) void trail_potf2_kernel(TrailArgs t, double *A
     return;
   }
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if (t.diag_updated) {   // nothing left to update: the stand-alone kernel's sweep, the first leaf straight from memory
+    potf2v4_run(Adiag, t.lda, nb, uinv, info, k0n, *reinterpret_cast<Leaf4Shared *>(smem), tid);
+    return;
+  }
   if (pivot_wave) {
     if (wave == 0) fused_diag_wave4<0>(t, Adiag, nb, uinv, info, k0n, smem, tid);
     else if (wave == 1) fused_diag_wave4<1>(t, Adiag, nb, uinv, info, k0n, smem, tid);
@@ -1196,7 +1213,8 @@ bool trail_potf2_available() {
 }
 
 hipError_t launch_trail_potf2(hipStream_t st, const double *P, double *C, int64_t lda, int64_t mrest,
-                              int64_t rest, int nb_next, double *uinv_next, int32_t *info, int32_t k0_next) {
+                              int64_t rest, int nb_next, double *uinv_next, int32_t *info, int32_t k0_next,
+                              double *pristine_out, bool diag_updated) {
   {
     const hipError_t ea = g_trail_attr.run([] {
       return hipFuncSetAttribute(reinterpret_cast<const void *>(trail_potf2_kernel),
@@ -1208,12 +1226,14 @@ hipError_t launch_trail_potf2(hipStream_t st, const double *P, double *C, int64_
   t.P = P; t.C = C; t.lda = lda;
   t.tiles_m = (int32_t)(mrest / 128);
   t.tiles_n = (int32_t)(rest / 128);
+  t.pristine = t.tiles_n >= 2 ? pristine_out : nullptr;
   static const int v4 = [] { const char *e = getenv("LSQAMD_POTF2"); return (!e || (e[0] == 'v' && e[1] == '4')) ? 1 : 0; }();
   const int64_t n_upper = (int64_t)t.tiles_m * t.tiles_n - (int64_t)t.tiles_m * (t.tiles_m - 1) / 2;
   // one workgroup per CU (workgroup 0's LDS): more tiles than CUs means a second round of workgroups,
   // mostly empty -- 64-column halves (twice the workgroups, half the work each) fill the rounds better
   static const int64_t half_from = [] { const char *e = getenv("LSQAMD_TRAIL_HALVES"); return e ? atoll(e) : (int64_t)256; }();
   t.halves = (n_upper > half_from) ? 1 : 0;
+  t.diag_updated = (diag_updated && v4) ? 1 : 0;
   const int64_t n_wg = t.halves ? 2 * (n_upper - 1) + 1 : n_upper;
   hipLaunchKernelGGL(trail_potf2_kernel, dim3((unsigned)n_wg), dim3(256), TRAIL_KERNEL_LDS,
                      st, t, C, nb_next, uinv_next, info, k0_next, v4);
