@@ -248,6 +248,28 @@ size_t lsqamd_whiten_work_bytes(int64_t block_size, int32_t n_blocks);
 int lsqamd_whiten_blocks(void *stream, int64_t block_size, int32_t n_blocks, const double *cov, double svdcut,
                          double *wt_out, double *prec_out, void *dev_work, size_t work_bytes,
                          double *logdet_out, double *lam_min_out, double *lam_max_out, int32_t *status_out);
+/* The eigen-mode route itself (doc/source/overview.rst:1546-1606: `svdcut > 0` raises the eigenvalues of the
+ * correlation matrix below |svdcut| * lambda_max to that floor, :1595-1603 `svdcut < 0` drops those modes), for the
+ * blocks lsqamd_whiten_blocks hands back -- a covariance estimated from fewer samples than points is singular and
+ * always lands here.  n_blocks blocks of ONE size 2 <= B <= 256 (LSQAMD_EUNSUPPORTED beyond: LAPACK on the host),
+ * given as for lsqamd_whiten_blocks: correlation matrix -> batched cyclic Jacobi eigensolver, one workgroup per
+ * block -> weights, all on the device.  Outputs:
+ *   wt_out      device, [n_blocks][B][B]: Wt_b[i][k] = V[i][k] / (sd_i sqrt(lamreg_k)) over the kept modes k (the
+ *               first modes_out[b] columns; the others zero), NOT triangular (block_tri = 0 in lsqamd_set_data);
+ *   prec_out    device, [n_blocks][B][B] or NULL: Wt_b Wt_b^T = inv(C_b regulated) (pseudo-inverse when modes drop);
+ *   lam_out     device, [n_blocks][B]: eigenvalues of the correlation matrix, ascending, unregulated;
+ *   vec_out     device, [n_blocks][B][B] or NULL: their orthonormal eigenvectors as columns;
+ *   logdet_out  host [n_blocks]: sum of log lamreg over the kept modes + 2 sum log sd;
+ *   modes_out / nmod_out  host [n_blocks]: kept modes; modes below the floor (svdn);
+ *   sweeps_out  host [n_blocks] or NULL: Jacobi sweeps taken;
+ *   status_out  host [n_blocks]: 0 = valid; 1 = take the host route for this block: the eigensolver did not
+ *               converge within its sweep bound, or the result hangs on rounding (a kept, unraised eigenvalue below
+ *               1e9 B eps lambda_max, or one within 16 B eps lambda_max of the floor); 2 = a variance or a kept regulated eigenvalue is not positive. */
+size_t lsqamd_whiten_eig_work_bytes(int64_t block_size, int32_t n_blocks);
+int lsqamd_whiten_blocks_eig(void *stream, int64_t block_size, int32_t n_blocks, const double *cov, double svdcut,
+                             double *wt_out, double *prec_out, double *lam_out, double *vec_out, void *dev_work,
+                             size_t work_bytes, double *logdet_out, int32_t *modes_out, int32_t *nmod_out,
+                             int32_t *sweeps_out, int32_t *status_out);
 
 /* ---- problem data (copied host -> device) ----------------------------------- */
 /* x[n_data][n_x]: what the closure `flatfcn` hides (__init__.py:566-568,:1997-2042) */

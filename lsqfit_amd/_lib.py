@@ -55,6 +55,10 @@ PROTOTYPES = {
     'lsqamd_whiten_work_bytes': (C.c_size_t, [C.c_int64, C.c_int32]),
     'lsqamd_whiten_blocks': (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_double, _vp, _vp, _vp, C.c_size_t,
                                        _dp, _dp, _dp, C.POINTER(C.c_int32)]),
+    'lsqamd_whiten_eig_work_bytes': (C.c_size_t, [C.c_int64, C.c_int32]),
+    'lsqamd_whiten_blocks_eig': (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
+                                           _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int32)]),
     'lsqamd_set_x': (C.c_int, [_vp, _dp, C.c_int64, C.c_int32]),
     'lsqamd_set_tape': (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int32, _dp, C.c_int32]),
     'lsqamd_set_data': (C.c_int, [_vp, _dp, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),

@@ -230,6 +230,15 @@ hipError_t backsolve_upper_batched(hipStream_t st, const double *A, int64_t n, i
 hipError_t trtri_upper_to_lower_T_batched(hipStream_t st, const double *A, int64_t n, int64_t lda,
                                           const double *work, double *Wl, int64_t ldw, int32_t batch,
                                           int64_t strideA, int64_t strideW, int64_t strideWl);
+// ---- batched symmetric eigensolver (eigh_blocks.hip) ------------------------------
+// nb symmetric B x B matrices (2 <= B <= kEighBlocksMax; matrix b at A + b*strideA, leading dimension lda), one
+// workgroup each: A_b is overwritten with its orthonormal eigenvectors as columns, lam[b][B] ascending;
+// sweeps[b]; status[b] = 0, or 1 when the block did not converge (its numbers are then not to be used).
+// slab: eigh_blocks_slab_doubles(B, lda) doubles per matrix (0 for B <= 64: everything lives in LDS)
+constexpr int64_t kEighBlocksMax = 256;
+size_t eigh_blocks_slab_doubles(int64_t B, int64_t lda);
+hipError_t launch_eigh_blocks(hipStream_t st, double *A, int64_t B, int64_t lda, int64_t strideA, int32_t nb, double *slab,
+                              double *lam, int32_t *sweeps, int32_t *status);
 // v = U^-1 y (y = column `ycol` of A rows 0..n-1), using the diagonal-block inverses in work
 // scratch (backsolve_scratch_bytes(n), with info_dev): the one-launch chain of workgroups (n a multiple of 128)
 size_t backsolve_scratch_bytes(int64_t n);

@@ -14,8 +14,9 @@
 // (lambda_max <= max_i sum_j |corr_ij|, lambda_min >= 1 / |Wl|_F^2 since |inv(corr)|_2 <= tr inv(corr)),
 // then -- only for blocks the bounds leave undecided -- inverse iteration with the factor
 // (u <- Wl^T Wl u, 40 sweeps).  Blocks whose floor may bind (status 1) or that are not positive
-// definite (status 2) go to the host's eigen route (lsqfit_amd/whiten.py), which is what gvar does
-// for every block.
+// definite (status 2) take the eigen route, which is what gvar does for every block:
+// lsqamd_whiten_blocks_eig below (eigh_blocks.hip's batched Jacobi solver + eig_weights_kernel) up to
+// 256 rows, LAPACK on the host (lsqfit_amd/whiten.py) above.
 #include <cmath>
 #include <vector>
 
@@ -154,6 +155,107 @@ Plan make_plan(int64_t B, int64_t nb, void *base) {
   return p;
 }
 
+// The weights of the eigen-mode route (doc/source/overview.rst:1546-1606) from (lam ascending, V) of the correlation
+// matrix, as lsqfit_amd/whiten.py:_regulate_block makes them; one workgroup per block.  floor = |svdcut| lam_max:
+// svdcut > 0 raises the nmod modes below it to the floor, svdcut < 0 drops them (kept columns move to the front, the
+// rest of Wt is zero).  Wt[i][k] = V[i][k] / (sd_i sqrt(lamreg_k)), contiguous B x B; W (or null) = Wt transposed
+// with leading dimension ldW, for inv(C) = W^T W; vec (or null) = V, contiguous.  status: the solver's on entry;
+// on exit 2 when a variance or a kept lamreg is not positive, 1 when the result would hang on rounding (below);
+// the weights are then not to be used.
+__global__ __launch_bounds__(256) void eig_weights_kernel(const double *V, int64_t B, int64_t ldv, int64_t strideV,
+                                                          const double *lam, const double *sd, const double *logsd,
+                                                          const int32_t *bad, double svdcut, double *wt, double *W,
+                                                          int64_t ldW, int64_t strideW, double *vec, double *logdet,
+                                                          int32_t *modes, int32_t *nmod, int32_t *status) {
+  __shared__ double rs[256];      // 1 / sqrt(lamreg_k), 0 for a dropped mode
+  __shared__ double sh[4];
+  __shared__ int n_low, not_pd, fragile;
+  const int64_t b = blockIdx.x;
+  const int t = threadIdx.x;
+  const double *l = lam + b * B, *s = sd + b * B, *v = V + b * strideV;
+  if (t == 0) n_low = not_pd = fragile = 0;
+  __syncthreads();
+  const double cut = fabs(svdcut), floor = cut * l[B - 1];
+  const bool low = t < B && cut != 0.0 && l[t] < floor;
+  if (low) atomicAdd(&n_low, 1);
+  __syncthreads();
+  const int nm = n_low, first = svdcut < 0.0 ? nm : 0;   // lam ascends: the low modes are the first nm
+  double acc = 0.0;
+  if (t < B) {
+    const double lr = low && svdcut > 0.0 ? floor : l[t];
+    const bool kept = t >= first;
+    if (kept && !(lr > 0.0 && lr < 1.0e300)) not_pd = 1;
+    // The solver's eigenvalues are good to ~ B eps lam_max ABSOLUTELY (as LAPACK's are).  Where the result leans on more than
+    // that -- a mode kept at its own value so small that its relative error passes 1e-9, or a mode within rounding of the
+    // floor, so that nmod hangs on it -- the numbers are rounding-dependent, and the block goes to the host, whose LAPACK
+    // route gives the bits the reference's own eigh gives (the printed fits of examples/y-noerr.out ride on them).
+    const double unit = (double)B * 2.220446049250313e-16 * l[B - 1];
+    if ((kept && !low && lr < 1.0e9 * unit) || (cut != 0.0 && fabs(l[t] - floor) < 16.0 * unit)) fragile = 1;
+    rs[t] = kept && lr > 0.0 ? 1.0 / sqrt(lr) : 0.0;
+    acc = kept && lr > 0.0 ? log(lr) : 0.0;
+  }
+  acc = wsum_w(acc);
+  if ((t & 63) == 0) sh[t >> 6] = acc;
+  __syncthreads();
+  if (t == 0) {
+    logdet[b] = sh[0] + sh[1] + sh[2] + sh[3] + 2.0 * logsd[b];
+    modes[b] = (int32_t)(B - first);
+    nmod[b] = nm;
+    if (bad[b] || not_pd) status[b] = 2;
+    else if (fragile && status[b] == 0) status[b] = 1;
+  }
+  for (int64_t idx = t; idx < B * B; idx += 256) {
+    const int64_t i = idx / B, k = idx - i * B, src = k + first;
+    const double w = src < B ? v[i * ldv + src] * rs[src] / s[i] : 0.0;
+    wt[b * B * B + idx] = w;
+    if (W) W[b * strideW + k * ldW + i] = w;
+    if (vec) vec[b * B * B + idx] = v[i * ldv + k];
+  }
+}
+
+// dst_b[i][0 .. B) = src_b[i][0 .. B): contiguous B x B blocks -> blocks with leading dimension ldd
+__global__ __launch_bounds__(256) void spread_rows_kernel(const double *src, int64_t B, double *dst, int64_t ldd) {
+  const int64_t i = blockIdx.x, b = blockIdx.y;
+  for (int64_t j = threadIdx.x; j < B; j += 256) dst[(b * B + i) * ldd + j] = src[(b * B + i) * B + j];
+}
+
+struct EigPlan {
+  int64_t ldw, strideA, strideS;
+  double *A, *slab, *W, *sd, *rowsum, *logsd, *logdet;
+  int32_t *modes, *nmod, *sweeps, *status, *bad;
+  size_t bytes, readback;
+};
+
+EigPlan make_eig_plan(int64_t B, int64_t nb, void *base) {
+  EigPlan p;
+  p.ldw = rup(B, 16);
+  p.strideA = B * p.ldw;
+  p.strideS = (int64_t)eigh_blocks_slab_doubles(B, p.ldw);
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    void *q = base ? (char *)base + off : nullptr;
+    off += (bytes + 255) / 256 * 256;
+    return q;
+  };
+  p.A = (double *)take(sizeof(double) * nb * p.strideA);          // covariance -> correlation -> eigenvectors, in place
+  p.slab = (double *)take(sizeof(double) * nb * p.strideS);       // the solver's columns (B > 64); free again behind it
+  // W = Wt^T for inv(C): in the slab where there is one, in a buffer of its own for the LDS-resident sizes
+  p.W = p.strideS ? p.slab : (double *)take(sizeof(double) * nb * p.strideA);
+  p.sd = (double *)take(sizeof(double) * nb * B);
+  p.rowsum = (double *)take(sizeof(double) * nb * B);
+  p.logsd = (double *)take(sizeof(double) * nb);
+  // (what the host reads back, in one piece: logdet .. bad)
+  p.logdet = (double *)take(sizeof(double) * nb);
+  p.modes = (int32_t *)take(sizeof(int32_t) * nb);
+  p.nmod = (int32_t *)take(sizeof(int32_t) * nb);
+  p.sweeps = (int32_t *)take(sizeof(int32_t) * nb);
+  p.status = (int32_t *)take(sizeof(int32_t) * nb);
+  p.bad = (int32_t *)take(sizeof(int32_t) * nb);
+  p.readback = (size_t)((char *)p.bad - (char *)p.logdet) + sizeof(int32_t) * (size_t)nb;
+  p.bytes = off;
+  return p;
+}
+
 #define WCHK(expr)                          \
   do {                                      \
     if ((expr) != hipSuccess) return LSQAMD_EHIP; \
@@ -261,6 +363,71 @@ int lsqamd_whiten_blocks(void *stream, int64_t B, int32_t nb, const double *cov,
     status_out[b] = status;
     if (lam_min_out) lam_min_out[b] = lo;
     if (lam_max_out) lam_max_out[b] = hi;
+  }
+  return 0;
+} LSQAMD_ABI_CATCH(return lsqamd::abi_exception(nullptr);)
+
+// The eigen-mode route (doc/source/overview.rst:1546-1606) for the blocks lsqamd_whiten_blocks hands back, 2 <= B <= 256:
+// copy in -> sdev / correlation -> batched Jacobi eigensolver (eigh_blocks.hip) -> weights -> inv(C) where wanted.
+size_t lsqamd_whiten_eig_work_bytes(int64_t block_size, int32_t n_blocks) try {
+  if (block_size < 2 || block_size > kEighBlocksMax || n_blocks < 1) return 0;
+  return make_eig_plan(block_size, n_blocks, nullptr).bytes + 256;
+} LSQAMD_ABI_CATCH((void)lsqamd::abi_exception(nullptr); return 0;)
+
+int lsqamd_whiten_blocks_eig(void *stream, int64_t B, int32_t nb, const double *cov, double svdcut, double *wt_out,
+                             double *prec_out, double *lam_out, double *vec_out, void *dev_work, size_t work_bytes,
+                             double *logdet_out, int32_t *modes_out, int32_t *nmod_out, int32_t *sweeps_out,
+                             int32_t *status_out) try {
+  if (nb < 1 || !cov || !wt_out || !lam_out || !dev_work || !logdet_out || !modes_out || !nmod_out || !status_out)
+    return LSQAMD_EINVAL;
+  if (B < 2 || B > kEighBlocksMax) return LSQAMD_EUNSUPPORTED;      // larger blocks: the caller's LAPACK route
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  char *base = (char *)dev_work;
+  const size_t pad = (size_t)((-(intptr_t)base) & 255);
+  if (work_bytes < pad) return LSQAMD_ENOMEM;
+  EigPlan p = make_eig_plan(B, nb, base + pad);
+  if (work_bytes < p.bytes + pad) return LSQAMD_ENOMEM;
+  const int64_t ldw = p.ldw, sA = p.strideA;
+  // ONE contiguous copy (a pitched copy from pageable memory goes row by row: nb * B small transfers); rows are spread to
+  // the leading dimension on the device, through wt_out, which nothing has written yet
+  if (ldw == B) {
+    WCHK(hipMemcpyAsync(p.A, cov, sizeof(double) * nb * B * B, hipMemcpyDefault, st));
+  } else {
+    WCHK(hipMemcpyAsync(wt_out, cov, sizeof(double) * nb * B * B, hipMemcpyDefault, st));
+    hipLaunchKernelGGL(spread_rows_kernel, dim3((unsigned)B, (unsigned)nb), dim3(256), 0, st, wt_out, B, p.A, ldw);
+  }
+  WCHK(hipMemsetAsync(p.bad, 0, sizeof(int32_t) * nb, st));
+  hipLaunchKernelGGL(sdev_kernel, dim3((unsigned)nb), dim3(256), 0, st, p.A, B, ldw, sA, p.sd, p.logsd, p.bad);
+  hipLaunchKernelGGL(to_corr_kernel, dim3((unsigned)((B + 3) / 4), (unsigned)nb), dim3(256), 0, st, p.A, B, ldw, sA,
+                     p.sd, p.rowsum);
+  WCHK(launch_eigh_blocks(st, p.A, B, ldw, sA, nb, p.slab, lam_out, p.sweeps, p.status));
+  const int64_t sW = p.strideS ? p.strideS : sA;
+  hipLaunchKernelGGL(eig_weights_kernel, dim3((unsigned)nb), dim3(256), 0, st, p.A, B, ldw, sA, lam_out, p.sd, p.logsd,
+                     p.bad, svdcut, wt_out, prec_out ? p.W : nullptr, ldw, sW, vec_out, p.logdet, p.modes, p.nmod,
+                     p.status);
+  if (prec_out) {
+    GemmTN g;   // inv(C_b) = Wt_b Wt_b^T = W_b^T W_b (full operands; upper tiles, then mirrored)
+    g.X = p.W; g.Y = p.W; g.ldx = g.ldy = ldw; g.sx = g.sy = sW;
+    g.C = prec_out; g.ldc = B; g.sc = B * B;
+    g.M = B; g.N = B; g.K = B;
+    g.upper_only = 1;
+    g.batch = nb;
+    WCHK(launch_gemm_tn(st, g));
+    for (int32_t b = 0; b < nb; ++b) WCHK(launch_symmetrize_from_upper(st, prec_out + (int64_t)b * B * B, B, B));
+  }
+  std::vector<char> back(p.readback);   // one copy for everything the host reads
+  WCHK(hipMemcpyAsync(back.data(), p.logdet, p.readback, hipMemcpyDeviceToHost, st));
+  WCHK(hipStreamSynchronize(st));
+  auto at = [&](const void *dev) { return back.data() + ((const char *)dev - (const char *)p.logdet); };
+  const double *logdet = (const double *)at(p.logdet);
+  const int32_t *modes = (const int32_t *)at(p.modes), *nmod = (const int32_t *)at(p.nmod);
+  const int32_t *sweeps = (const int32_t *)at(p.sweeps), *status = (const int32_t *)at(p.status);
+  for (int32_t b = 0; b < nb; ++b) {
+    logdet_out[b] = logdet[b];
+    modes_out[b] = modes[b];
+    nmod_out[b] = nmod[b];
+    if (sweeps_out) sweeps_out[b] = sweeps[b];
+    status_out[b] = status[b] == 0 && !std::isfinite(logdet[b]) ? 2 : status[b];
   }
   return 0;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(nullptr);)

@@ -9,8 +9,9 @@ Cholesky of the correlation matrices, triangular inverses, log-determinants, the
 test whether the svdcut floor can bind; the weights stay in HBM and go straight
 into ``lsqamd_set_data`` / ``lsqamd_set_prior``).  Only a block whose floor DOES
 bind (or that is not positive definite) takes the eigen-mode route of
-doc/source/overview.rst:1546-1606 in LAPACK on the host -- which is what gvar does
-for every block.  Without a visible GPU (the host-logic tests) everything takes the
+doc/source/overview.rst:1546-1606 -- which is what gvar does for every block: up to
+256 rows on the device as well (``lsqamd_whiten_blocks_eig``, a batched Jacobi
+eigensolver), in LAPACK on the host above that.  Without a visible GPU (the host-logic tests) everything takes the
 LAPACK route; nothing can be fitted there anyway.  It produces what the device path
 consumes through ``lsqamd_set_data`` / ``lsqamd_set_prior``:
 
@@ -33,6 +34,8 @@ to x and un-does in its row-ordered outputs.  Data-prior cross-correlations
 whitened as ONE vector, exactly as the reference does, and the prior entries
 travel to the device as extra "parameter rows" (lsqamd_set_param_rows).
 """
+import os
+
 import numpy as np
 import scipy.linalg as sla
 
@@ -67,6 +70,14 @@ def _regulate_block(cov, svdcut, force_eig=False):
         return dict(Wt=np.ascontiguousarray(W.T), modes=B, tri=1, logdet=logdet, nmod=0,
                     var_reg=sd ** 2, S=sd[:, None] * L)
     lam, vec = np.linalg.eigh(corr)
+    return _eig_forms(lam, vec, sd, cut)
+
+
+def _eig_forms(lam, vec, sd, cut):
+    """What the eigen-mode route makes of (lam ascending, vec) of a block's correlation matrix
+    (doc/source/overview.rst:1546-1606); also the lazily made host forms of a block whose eigenpairs
+    came from the device (:class:`_Block`)."""
+    B = lam.size
     keep = np.ones(B, bool)
     lam_reg = lam.copy()
     nmod = 0
@@ -113,9 +124,25 @@ class _Block(dict):
         side.synchronize()
         return h.numpy()
 
+    def has_S_add(self):
+        """True when the svdcut floor raised modes: ``self['S_add']`` exists (a block whose eigenpairs are on the device makes
+        it on first use)."""
+        return 'S_add' in self or ('lam_dev' in self and self['svdcut'] > 0 and self['nmod'] > 0)
+
     def __missing__(self, key):
         if key == 'Wt':
             v = self._to_host(self['Wt_dev'])
+        elif key in ('S', 'S_add', 'var_reg') and 'lam_dev' in self:
+            # eigen-mode block made on the device: the host forms come from its (lam, vec), never from a Cholesky
+            # factor of the unregulated block (which is singular here)
+            forms = _eig_forms(self._to_host(self['lam_dev']), self._to_host(self['vec_dev']),
+                               np.sqrt(np.diag(self['cov'])), self['svdcut'])
+            for k in ('S', 'S_add', 'var_reg'):
+                if k in forms:
+                    self.setdefault(k, forms[k])
+            if key not in self:
+                raise KeyError(key)
+            return self[key]
         elif key == 'S':
             cov = np.asarray(self['cov'], float)
             sd = np.sqrt(np.diag(cov))
@@ -176,15 +203,84 @@ def _device_regulate(covs, svdcut, want_prec):
     return out
 
 
+EIGH_DEVICE_MAX = 256      # largest block of the device's eigensolver (csrc/eigh_blocks.hip); above it: LAPACK
+# Measured crossover (profiles/eigh_blocks.txt, section 2): the solver's time is a chain of barrier steps that hardly depends on
+# the number of blocks (one workgroup each), LAPACK's grows with it.  Fewest same-size blocks in one call at which the device
+# route was measured faster at every size scanned (B = 16, 64, 128, 256: 0.74-0.85 x the host's time at 64 blocks, 1.1-1.6 x
+# at 16 for B >= 64); smaller batches stay on the host.
+EIGH_DEVICE_MIN_BLOCKS = 64
+
+
+def _eigh_on_device(B, n_blocks):
+    """Route n_blocks handed-back blocks of size B to the device's eigensolver?  ``LSQAMD_EIGH`` (read per call): ``host``
+    never, ``device`` whenever the solver takes the size, otherwise by the measured crossover."""
+    knob = os.environ.get('LSQAMD_EIGH', '')
+    if knob == 'host' or not 2 <= B <= EIGH_DEVICE_MAX:
+        return False
+    return knob == 'device' or n_blocks >= EIGH_DEVICE_MIN_BLOCKS
+
+
+def _device_regulate_eig(covs, svdcut, want_prec):
+    """Same-size covariance blocks (2 <= B <= EIGH_DEVICE_MAX) the Cholesky route handed back ->
+    [_Block or None] through ``lsqamd_whiten_blocks_eig``: the eigen-mode route on the device, ONE call
+    for all of them.  None marks a block for the host: the eigensolver did not converge, the result
+    would hang on rounding (an eigenvalue that matters within the solver's absolute accuracy of zero or of
+    the floor: LAPACK gives the reference's bits there), or the block is not positive definite (the host
+    route raises the error for it)."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    nb, B = len(covs), covs[0].shape[0]
+    cut = 0.0 if svdcut is None else float(svdcut)
+    stack = np.ascontiguousarray(covs[0] if nb == 1 else np.stack(covs), np.float64)
+    dev = torch.device('cuda', torch.cuda.current_device())
+    side = _lib.side_stream(dev)
+    i32 = C.POINTER(C.c_int32)
+    with torch.cuda.stream(side):
+        wt = torch.empty((nb, B, B), dtype=torch.float64, device=dev)
+        prec = torch.empty((nb, B, B), dtype=torch.float64, device=dev) if want_prec else None
+        lam = torch.empty((nb, B), dtype=torch.float64, device=dev)
+        vec = torch.empty((nb, B, B), dtype=torch.float64, device=dev)
+        nbytes = lib.lsqamd_whiten_eig_work_bytes(B, nb)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        logdet = np.empty(nb)
+        modes, nmod, sweeps, status = (np.empty(nb, np.int32) for _ in range(4))
+        rc = lib.lsqamd_whiten_blocks_eig(
+            C.c_void_p(side.cuda_stream), B, nb, C.c_void_p(stack.ctypes.data), cut, C.c_void_p(wt.data_ptr()),
+            C.c_void_p(prec.data_ptr()) if want_prec else None, C.c_void_p(lam.data_ptr()), C.c_void_p(vec.data_ptr()),
+            C.c_void_p(work.data_ptr()), nbytes, _lib.dptr(logdet), modes.ctypes.data_as(i32), nmod.ctypes.data_as(i32),
+            sweeps.ctypes.data_as(i32), status.ctypes.data_as(i32))
+        side.synchronize()
+    if rc != 0:
+        raise RuntimeError('lsqfit_amd: lsqamd_whiten_blocks_eig failed (%s)' % _lib.ERRORS.get(rc, rc))
+    del work
+    out = []
+    for b in range(nb):
+        if status[b] != 0:
+            out.append(None)
+            continue
+        k = _Block(Wt_dev=wt[b], modes=int(modes[b]), tri=0, logdet=float(logdet[b]), nmod=int(nmod[b]), cov=covs[b],
+                   lam_dev=lam[b], vec_dev=vec[b], svdcut=cut, sweeps=int(sweeps[b]))
+        if want_prec:
+            k['prec_dev'] = prec[b]
+        out.append(k)
+    return out
+
+
 def regulate_blocks(covs, svdcut, want_prec=False, engine=None):
     """[cov] -> [_Block]: the factorisations of every correlated block, on the device when one is
-    visible (``engine`` None), grouped by block size; LAPACK eigen route for what the device hands
-    back and for ``engine='host'``."""
+    visible (``engine`` None), grouped by block size: Cholesky where the svdcut floor touches no
+    mode, the batched eigensolver for the blocks that hands back (up to EIGH_DEVICE_MAX rows, at
+    least EIGH_DEVICE_MIN_BLOCKS of one size: :func:`_eigh_on_device`).  LAPACK eigen route for the
+    others, for a block the eigensolver hands on (``'eig_handed_back'`` is set on it: it was solved
+    twice) and for ``engine='host'`` / ``'eig'``."""
     if engine is None:
         engine = 'device' if device_available() else 'host'
     if engine not in ('device', 'host', 'eig'):
         raise ValueError("engine must be 'device', 'host' or 'eig'")
     out = [None] * len(covs)
+    solved_twice = set()          # blocks the device's eigensolver handed on to LAPACK: marked, so a caller can count them
     if engine == 'device':
         by_size = {}
         for i, c in enumerate(covs):
@@ -192,12 +288,20 @@ def regulate_blocks(covs, svdcut, want_prec=False, engine=None):
         for B, idx in by_size.items():
             for i, k in zip(idx, _device_regulate([np.asarray(covs[i], float) for i in idx], svdcut, want_prec)):
                 out[i] = k
+            back = [i for i in idx if out[i] is None]
+            if back and _eigh_on_device(B, len(back)):
+                for i, k in zip(back, _device_regulate_eig([np.asarray(covs[i], float) for i in back], svdcut, want_prec)):
+                    out[i] = k
+                    if k is None:
+                        solved_twice.add(i)
     for i, c in enumerate(covs):
         if out[i] is None:
             # 'eig': every block through its eigen-modes, the basis gvar whitens in -- needed where the fit is NOT invariant under
             # a rotation of a block's whitened rows (robust losses, rows_whitening)
             out[i] = _Block(_regulate_block(c, svdcut, force_eig=(engine in ('device', 'eig'))))
             out[i]['cov'] = np.asarray(c, float)
+            if i in solved_twice:
+                out[i]['eig_handed_back'] = True
     return out
 
 
@@ -323,7 +427,7 @@ class Whitening:
             self.logdet += reg['logdet']
             self.nmod += B if eps else reg['nmod']
             self.nblocks[B] = self.nblocks.get(B, 0) + 1
-            if 'S_add' in reg:
+            if self.noise[0] and reg.has_S_add():      # (only a noisy fit reads it: a device-made block fetches it on demand)
                 added.append((int(r0), reg['S_add']))
         if self.noise[0] and added:
             gen = np.random.default_rng(rng)
