@@ -251,9 +251,10 @@ int lsqamd_whiten_blocks(void *stream, int64_t block_size, int32_t n_blocks, con
 /* The eigen-mode route itself (doc/source/overview.rst:1546-1606: `svdcut > 0` raises the eigenvalues of the
  * correlation matrix below |svdcut| * lambda_max to that floor, :1595-1603 `svdcut < 0` drops those modes), for the
  * blocks lsqamd_whiten_blocks hands back -- a covariance estimated from fewer samples than points is singular and
- * always lands here.  n_blocks blocks of ONE size 2 <= B <= 256 (LSQAMD_EUNSUPPORTED beyond: LAPACK on the host),
- * given as for lsqamd_whiten_blocks: correlation matrix -> batched cyclic Jacobi eigensolver, one workgroup per
- * block -> weights, all on the device.  Outputs:
+ * always lands here.  n_blocks blocks of ONE size 2 <= B <= 8192 (LSQAMD_EUNSUPPORTED beyond: LAPACK on the host),
+ * given as for lsqamd_whiten_blocks: correlation matrix -> batched Jacobi eigensolver (cyclic one-sided, one workgroup
+ * per block, up to 256 rows; two-sided block Jacobi on the matrix pipe above, which synchronises the stream once per
+ * sweep) -> weights, all on the device.  Outputs:
  *   wt_out      device, [n_blocks][B][B]: Wt_b[i][k] = V[i][k] / (sd_i sqrt(lamreg_k)) over the kept modes k (the
  *               first modes_out[b] columns; the others zero), NOT triangular (block_tri = 0 in lsqamd_set_data);
  *   prec_out    device, [n_blocks][B][B] or NULL: Wt_b Wt_b^T = inv(C_b regulated) (pseudo-inverse when modes drop);

@@ -239,6 +239,15 @@ constexpr int64_t kEighBlocksMax = 256;
 size_t eigh_blocks_slab_doubles(int64_t B, int64_t lda);
 hipError_t launch_eigh_blocks(hipStream_t st, double *A, int64_t B, int64_t lda, int64_t strideA, int32_t nb, double *slab,
                               double *lam, int32_t *sweeps, int32_t *status);
+// the same contract for kEighBlocksMax < B <= kEighLargeMax (eigh_large.hip: two-sided block Jacobi, rotations on fp64 MFMA,
+// the 64 x 64 pivots through launch_eigh_blocks).  A_b needs room for Bp = B rounded up to 32 rows and columns: lda >= Bp,
+// strideA >= Bp * lda (the padding is overwritten).  scratch: eigh_large_scratch_doubles(B, nb) doubles for ALL nb matrices;
+// its first nb * Bp * Bp doubles are free for the caller again when the call returns.  Synchronises the stream once per sweep.
+constexpr int64_t kEighLargeMax = 8192;
+constexpr int32_t kEighLargeBatchMax = 32767;   // nb: the rotations' grid holds 2 nb in z; the caller splits a larger batch
+size_t eigh_large_scratch_doubles(int64_t B, int32_t nb);
+hipError_t launch_eigh_large(hipStream_t st, double *A, int64_t B, int64_t lda, int64_t strideA, int32_t nb, double *scratch,
+                             double *lam, int32_t *sweeps, int32_t *status);
 // v = U^-1 y (y = column `ycol` of A rows 0..n-1), using the diagonal-block inverses in work
 // scratch (backsolve_scratch_bytes(n), with info_dev): the one-launch chain of workgroups (n a multiple of 128)
 size_t backsolve_scratch_bytes(int64_t n);

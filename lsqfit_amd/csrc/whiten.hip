@@ -15,8 +15,8 @@
 // then -- only for blocks the bounds leave undecided -- inverse iteration with the factor
 // (u <- Wl^T Wl u, 40 sweeps).  Blocks whose floor may bind (status 1) or that are not positive
 // definite (status 2) take the eigen route, which is what gvar does for every block:
-// lsqamd_whiten_blocks_eig below (eigh_blocks.hip's batched Jacobi solver + eig_weights_kernel) up to
-// 256 rows, LAPACK on the host (lsqfit_amd/whiten.py) above.
+// lsqamd_whiten_blocks_eig below (the batched Jacobi solvers of eigh_blocks.hip, up to 256 rows, and eigh_large.hip, up
+// to 8192, + eig_weights_kernel), LAPACK on the host (lsqfit_amd/whiten.py) above that.
 #include <cmath>
 #include <vector>
 
@@ -166,33 +166,36 @@ __global__ __launch_bounds__(256) void eig_weights_kernel(const double *V, int64
                                                           const double *lam, const double *sd, const double *logsd,
                                                           const int32_t *bad, double svdcut, double *wt, double *W,
                                                           int64_t ldW, int64_t strideW, double *vec, double *logdet,
-                                                          int32_t *modes, int32_t *nmod, int32_t *status) {
-  __shared__ double rs[256];      // 1 / sqrt(lamreg_k), 0 for a dropped mode
+                                                          int32_t *modes, int32_t *nmod, int32_t *status, double *rs_big) {
+  __shared__ double rs_lds[256];  // 1 / sqrt(lamreg_k), 0 for a dropped mode (above 256 rows: rs_big, and eig_spread_kernel makes the weights)
   __shared__ double sh[4];
   __shared__ int n_low, not_pd, fragile;
   const int64_t b = blockIdx.x;
   const int t = threadIdx.x;
   const double *l = lam + b * B, *s = sd + b * B, *v = V + b * strideV;
+  double *rs = rs_big ? rs_big + b * B : rs_lds;
   if (t == 0) n_low = not_pd = fragile = 0;
   __syncthreads();
   const double cut = fabs(svdcut), floor = cut * l[B - 1];
-  const bool low = t < B && cut != 0.0 && l[t] < floor;
-  if (low) atomicAdd(&n_low, 1);
+  int cnt = 0;
+  for (int64_t k = t; k < B; k += 256) cnt += cut != 0.0 && l[k] < floor ? 1 : 0;
+  if (cnt) atomicAdd(&n_low, cnt);
   __syncthreads();
   const int nm = n_low, first = svdcut < 0.0 ? nm : 0;   // lam ascends: the low modes are the first nm
   double acc = 0.0;
-  if (t < B) {
-    const double lr = low && svdcut > 0.0 ? floor : l[t];
-    const bool kept = t >= first;
+  for (int64_t k = t; k < B; k += 256) {
+    const bool low = cut != 0.0 && l[k] < floor;
+    const double lr = low && svdcut > 0.0 ? floor : l[k];
+    const bool kept = k >= first;
     if (kept && !(lr > 0.0 && lr < 1.0e300)) not_pd = 1;
     // The solver's eigenvalues are good to ~ B eps lam_max ABSOLUTELY (as LAPACK's are).  Where the result leans on more than
     // that -- a mode kept at its own value so small that its relative error passes 1e-9, or a mode within rounding of the
     // floor, so that nmod hangs on it -- the numbers are rounding-dependent, and the block goes to the host, whose LAPACK
     // route gives the bits the reference's own eigh gives (the printed fits of examples/y-noerr.out ride on them).
     const double unit = (double)B * 2.220446049250313e-16 * l[B - 1];
-    if ((kept && !low && lr < 1.0e9 * unit) || (cut != 0.0 && fabs(l[t] - floor) < 16.0 * unit)) fragile = 1;
-    rs[t] = kept && lr > 0.0 ? 1.0 / sqrt(lr) : 0.0;
-    acc = kept && lr > 0.0 ? log(lr) : 0.0;
+    if ((kept && !low && lr < 1.0e9 * unit) || (cut != 0.0 && fabs(l[k] - floor) < 16.0 * unit)) fragile = 1;
+    rs[k] = kept && lr > 0.0 ? 1.0 / sqrt(lr) : 0.0;
+    acc += kept && lr > 0.0 ? log(lr) : 0.0;
   }
   acc = wsum_w(acc);
   if ((t & 63) == 0) sh[t >> 6] = acc;
@@ -204,6 +207,7 @@ __global__ __launch_bounds__(256) void eig_weights_kernel(const double *V, int64
     if (bad[b] || not_pd) status[b] = 2;
     else if (fragile && status[b] == 0) status[b] = 1;
   }
+  if (rs_big) return;
   for (int64_t idx = t; idx < B * B; idx += 256) {
     const int64_t i = idx / B, k = idx - i * B, src = k + first;
     const double w = src < B ? v[i * ldv + src] * rs[src] / s[i] : 0.0;
@@ -213,24 +217,44 @@ __global__ __launch_bounds__(256) void eig_weights_kernel(const double *V, int64
   }
 }
 
-// dst_b[i][0 .. B) = src_b[i][0 .. B): contiguous B x B blocks -> blocks with leading dimension ldd
-__global__ __launch_bounds__(256) void spread_rows_kernel(const double *src, int64_t B, double *dst, int64_t ldd) {
+// the weights pass of eig_weights_kernel for blocks above 256 rows: row i of Wt_b, column i of W_b; grid (B, nb)
+__global__ __launch_bounds__(256) void eig_spread_kernel(const double *V, int64_t B, int64_t ldv, int64_t strideV,
+                                                         const double *sd, const double *rs_big, double svdcut,
+                                                         const int32_t *nmod, double *wt, double *W, int64_t ldW,
+                                                         int64_t strideW, double *vec) {
   const int64_t i = blockIdx.x, b = blockIdx.y;
-  for (int64_t j = threadIdx.x; j < B; j += 256) dst[(b * B + i) * ldd + j] = src[(b * B + i) * B + j];
+  const double *v = V + b * strideV + i * ldv, *rs = rs_big + b * B;
+  const int64_t first = svdcut < 0.0 ? nmod[b] : 0;
+  const double si = sd[b * B + i];
+  for (int64_t k = threadIdx.x; k < B; k += 256) {
+    const int64_t src = k + first;
+    const double w = src < B ? v[src] * rs[src] / si : 0.0;
+    wt[(b * B + i) * B + k] = w;
+    if (W) W[b * strideW + k * ldW + i] = w;
+    if (vec) vec[(b * B + i) * B + k] = v[k];
+  }
+}
+
+// dst_b[i][0 .. B) = src_b[i][0 .. B): contiguous B x B blocks -> blocks with leading dimension ldd, strided apart
+__global__ __launch_bounds__(256) void spread_rows_kernel(const double *src, int64_t B, double *dst, int64_t ldd,
+                                                          int64_t strided) {
+  const int64_t i = blockIdx.x, b = blockIdx.y;
+  for (int64_t j = threadIdx.x; j < B; j += 256) dst[b * strided + i * ldd + j] = src[(b * B + i) * B + j];
 }
 
 struct EigPlan {
   int64_t ldw, strideA, strideS;
-  double *A, *slab, *W, *sd, *rowsum, *logsd, *logdet;
+  double *A, *slab, *W, *sd, *rowsum, *logsd, *logdet, *rs;
   int32_t *modes, *nmod, *sweeps, *status, *bad;
   size_t bytes, readback;
 };
 
 EigPlan make_eig_plan(int64_t B, int64_t nb, void *base) {
   EigPlan p;
-  p.ldw = rup(B, 16);
-  p.strideA = B * p.ldw;
-  p.strideS = (int64_t)eigh_blocks_slab_doubles(B, p.ldw);
+  const bool large = B > kEighBlocksMax;   // eigh_large.hip: rows and columns padded to 32, W in the solver's V when it is through
+  p.ldw = rup(B, large ? 32 : 16);
+  p.strideA = (large ? p.ldw : B) * p.ldw;
+  p.strideS = large ? p.ldw * p.ldw : (int64_t)eigh_blocks_slab_doubles(B, p.ldw);
   size_t off = 0;
   auto take = [&](size_t bytes) {
     void *q = base ? (char *)base + off : nullptr;
@@ -238,7 +262,9 @@ EigPlan make_eig_plan(int64_t B, int64_t nb, void *base) {
     return q;
   };
   p.A = (double *)take(sizeof(double) * nb * p.strideA);          // covariance -> correlation -> eigenvectors, in place
-  p.slab = (double *)take(sizeof(double) * nb * p.strideS);       // the solver's columns (B > 64); free again behind it
+  // the solver's columns (B > 64) or, above 256 rows, all of eigh_large's scratch; free again behind it
+  p.slab = (double *)take(sizeof(double) * (large ? eigh_large_scratch_doubles(B, (int32_t)nb) : (size_t)(nb * p.strideS)));
+  p.rs = large ? (double *)take(sizeof(double) * nb * B) : nullptr;   // eig_weights_kernel's 1 / sqrt(lamreg) (in LDS up to 256 rows)
   // W = Wt^T for inv(C): in the slab where there is one, in a buffer of its own for the LDS-resident sizes
   p.W = p.strideS ? p.slab : (double *)take(sizeof(double) * nb * p.strideA);
   p.sd = (double *)take(sizeof(double) * nb * B);
@@ -367,10 +393,11 @@ int lsqamd_whiten_blocks(void *stream, int64_t B, int32_t nb, const double *cov,
   return 0;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(nullptr);)
 
-// The eigen-mode route (doc/source/overview.rst:1546-1606) for the blocks lsqamd_whiten_blocks hands back, 2 <= B <= 256:
-// copy in -> sdev / correlation -> batched Jacobi eigensolver (eigh_blocks.hip) -> weights -> inv(C) where wanted.
+// The eigen-mode route (doc/source/overview.rst:1546-1606) for the blocks lsqamd_whiten_blocks hands back, 2 <= B <= 8192:
+// copy in -> sdev / correlation -> batched Jacobi eigensolver (eigh_blocks.hip up to 256 rows, eigh_large.hip above) ->
+// weights -> inv(C) where wanted.
 size_t lsqamd_whiten_eig_work_bytes(int64_t block_size, int32_t n_blocks) try {
-  if (block_size < 2 || block_size > kEighBlocksMax || n_blocks < 1) return 0;
+  if (block_size < 2 || block_size > kEighLargeMax || n_blocks < 1) return 0;
   return make_eig_plan(block_size, n_blocks, nullptr).bytes + 256;
 } LSQAMD_ABI_CATCH((void)lsqamd::abi_exception(nullptr); return 0;)
 
@@ -380,7 +407,8 @@ int lsqamd_whiten_blocks_eig(void *stream, int64_t B, int32_t nb, const double *
                              int32_t *status_out) try {
   if (nb < 1 || !cov || !wt_out || !lam_out || !dev_work || !logdet_out || !modes_out || !nmod_out || !status_out)
     return LSQAMD_EINVAL;
-  if (B < 2 || B > kEighBlocksMax) return LSQAMD_EUNSUPPORTED;      // larger blocks: the caller's LAPACK route
+  if (B < 2 || B > kEighLargeMax) return LSQAMD_EUNSUPPORTED;       // larger blocks: the caller's LAPACK route
+  if (B > kEighBlocksMax && nb > kEighLargeBatchMax) return LSQAMD_EUNSUPPORTED;   // (whiten.py splits such a batch)
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   char *base = (char *)dev_work;
   const size_t pad = (size_t)((-(intptr_t)base) & 255);
@@ -394,17 +422,22 @@ int lsqamd_whiten_blocks_eig(void *stream, int64_t B, int32_t nb, const double *
     WCHK(hipMemcpyAsync(p.A, cov, sizeof(double) * nb * B * B, hipMemcpyDefault, st));
   } else {
     WCHK(hipMemcpyAsync(wt_out, cov, sizeof(double) * nb * B * B, hipMemcpyDefault, st));
-    hipLaunchKernelGGL(spread_rows_kernel, dim3((unsigned)B, (unsigned)nb), dim3(256), 0, st, wt_out, B, p.A, ldw);
+    hipLaunchKernelGGL(spread_rows_kernel, dim3((unsigned)B, (unsigned)nb), dim3(256), 0, st, wt_out, B, p.A, ldw, sA);
   }
   WCHK(hipMemsetAsync(p.bad, 0, sizeof(int32_t) * nb, st));
   hipLaunchKernelGGL(sdev_kernel, dim3((unsigned)nb), dim3(256), 0, st, p.A, B, ldw, sA, p.sd, p.logsd, p.bad);
   hipLaunchKernelGGL(to_corr_kernel, dim3((unsigned)((B + 3) / 4), (unsigned)nb), dim3(256), 0, st, p.A, B, ldw, sA,
                      p.sd, p.rowsum);
-  WCHK(launch_eigh_blocks(st, p.A, B, ldw, sA, nb, p.slab, lam_out, p.sweeps, p.status));
+  const bool large = B > kEighBlocksMax;
+  if (large) WCHK(launch_eigh_large(st, p.A, B, ldw, sA, nb, p.slab, lam_out, p.sweeps, p.status));
+  else WCHK(launch_eigh_blocks(st, p.A, B, ldw, sA, nb, p.slab, lam_out, p.sweeps, p.status));
   const int64_t sW = p.strideS ? p.strideS : sA;
   hipLaunchKernelGGL(eig_weights_kernel, dim3((unsigned)nb), dim3(256), 0, st, p.A, B, ldw, sA, lam_out, p.sd, p.logsd,
                      p.bad, svdcut, wt_out, prec_out ? p.W : nullptr, ldw, sW, vec_out, p.logdet, p.modes, p.nmod,
-                     p.status);
+                     p.status, p.rs);
+  if (large)
+    hipLaunchKernelGGL(eig_spread_kernel, dim3((unsigned)B, (unsigned)nb), dim3(256), 0, st, p.A, B, ldw, sA, p.sd, p.rs,
+                       svdcut, p.nmod, wt_out, prec_out ? p.W : nullptr, ldw, sW, vec_out);
   if (prec_out) {
     GemmTN g;   // inv(C_b) = Wt_b Wt_b^T = W_b^T W_b (full operands; upper tiles, then mirrored)
     g.X = p.W; g.Y = p.W; g.ldx = g.ldy = ldw; g.sx = g.sy = sW;

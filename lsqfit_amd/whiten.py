@@ -10,8 +10,9 @@ test whether the svdcut floor can bind; the weights stay in HBM and go straight
 into ``lsqamd_set_data`` / ``lsqamd_set_prior``).  Only a block whose floor DOES
 bind (or that is not positive definite) takes the eigen-mode route of
 doc/source/overview.rst:1546-1606 -- which is what gvar does for every block: up to
-256 rows on the device as well (``lsqamd_whiten_blocks_eig``, a batched Jacobi
-eigensolver), in LAPACK on the host above that.  Without a visible GPU (the host-logic tests) everything takes the
+8192 rows the device can take it as well (``lsqamd_whiten_blocks_eig``: a batched Jacobi
+eigensolver up to 256 rows, block Jacobi on the matrix pipe above; :func:`_eigh_on_device`
+says when it does), LAPACK on the host otherwise.  Without a visible GPU (the host-logic tests) everything takes the
 LAPACK route; nothing can be fitted there anyway.  It produces what the device path
 consumes through ``lsqamd_set_data`` / ``lsqamd_set_prior``:
 
@@ -203,7 +204,9 @@ def _device_regulate(covs, svdcut, want_prec):
     return out
 
 
-EIGH_DEVICE_MAX = 256      # largest block of the device's eigensolver (csrc/eigh_blocks.hip); above it: LAPACK
+EIGH_DEVICE_MAX = 256      # largest block of the one-workgroup eigensolver (csrc/eigh_blocks.hip)
+EIGH_LARGE_MAX = 8192      # largest block of the block-Jacobi eigensolver (csrc/eigh_large.hip); above it: LAPACK
+EIGH_LARGE_BATCH_MAX = 32767   # most blocks of more than EIGH_DEVICE_MAX rows in one call (common.h: kEighLargeBatchMax)
 # Measured crossover (profiles/eigh_blocks.txt, section 2): the solver's time is a chain of barrier steps that hardly depends on
 # the number of blocks (one workgroup each), LAPACK's grows with it.  Fewest same-size blocks in one call at which the device
 # route was measured faster at every size scanned (B = 16, 64, 128, 256: 0.74-0.85 x the host's time at 64 blocks, 1.1-1.6 x
@@ -211,27 +214,44 @@ EIGH_DEVICE_MAX = 256      # largest block of the device's eigensolver (csrc/eig
 EIGH_DEVICE_MIN_BLOCKS = 64
 
 
+# Above EIGH_DEVICE_MAX rows (profiles/eigh_large.txt): (first size, last size, fewest blocks) of the ranges in which the
+# device route was measured faster than LAPACK at every size and every batch scanned; everywhere else it stays behind
+# LSQAMD_EIGH_LARGE=device.
+EIGH_LARGE_DEFAULT = ()
+
+
 def _eigh_on_device(B, n_blocks):
     """Route n_blocks handed-back blocks of size B to the device's eigensolver?  ``LSQAMD_EIGH`` (read per call): ``host``
-    never, ``device`` whenever the solver takes the size, otherwise by the measured crossover."""
+    never, ``device`` whenever the one-workgroup solver takes the size (up to EIGH_DEVICE_MAX rows), otherwise by the measured
+    crossover.  Above EIGH_DEVICE_MAX rows, up to EIGH_LARGE_MAX, ``LSQAMD_EIGH_LARGE`` (read per call) decides: ``device``
+    always, ``host`` never, otherwise only inside the measured ranges of EIGH_LARGE_DEFAULT."""
     knob = os.environ.get('LSQAMD_EIGH', '')
-    if knob == 'host' or not 2 <= B <= EIGH_DEVICE_MAX:
+    if knob == 'host' or not 2 <= B <= EIGH_LARGE_MAX:
         return False
+    if B > EIGH_DEVICE_MAX:
+        large = os.environ.get('LSQAMD_EIGH_LARGE', '')
+        if large in ('device', 'host'):
+            return large == 'device'
+        return any(lo <= B <= hi and n_blocks >= least for lo, hi, least in EIGH_LARGE_DEFAULT)
     return knob == 'device' or n_blocks >= EIGH_DEVICE_MIN_BLOCKS
 
 
-def _device_regulate_eig(covs, svdcut, want_prec):
-    """Same-size covariance blocks (2 <= B <= EIGH_DEVICE_MAX) the Cholesky route handed back ->
+def _device_regulate_eig(covs, svdcut, want_prec, words=None):
+    """Same-size covariance blocks (2 <= B <= EIGH_LARGE_MAX) the Cholesky route handed back ->
     [_Block or None] through ``lsqamd_whiten_blocks_eig``: the eigen-mode route on the device, ONE call
     for all of them.  None marks a block for the host: the eigensolver did not converge, the result
     would hang on rounding (an eigenvalue that matters within the solver's absolute accuracy of zero or of
     the floor: LAPACK gives the reference's bits there), or the block is not positive definite (the host
-    route raises the error for it)."""
+    route raises the error for it).  ``words``: a list that takes the solver's (sweeps, status) arrays of every call made,
+    handed-back blocks included."""
     import ctypes as C
     import torch
     from . import _lib
     lib = _lib.load()
     nb, B = len(covs), covs[0].shape[0]
+    if B > EIGH_DEVICE_MAX and nb > EIGH_LARGE_BATCH_MAX:
+        return [k for i in range(0, nb, EIGH_LARGE_BATCH_MAX)
+                for k in _device_regulate_eig(covs[i:i + EIGH_LARGE_BATCH_MAX], svdcut, want_prec, words)]
     cut = 0.0 if svdcut is None else float(svdcut)
     stack = np.ascontiguousarray(covs[0] if nb == 1 else np.stack(covs), np.float64)
     dev = torch.device('cuda', torch.cuda.current_device())
@@ -255,6 +275,8 @@ def _device_regulate_eig(covs, svdcut, want_prec):
     if rc != 0:
         raise RuntimeError('lsqfit_amd: lsqamd_whiten_blocks_eig failed (%s)' % _lib.ERRORS.get(rc, rc))
     del work
+    if words is not None:
+        words.append((sweeps, status))
     out = []
     for b in range(nb):
         if status[b] != 0:
@@ -271,8 +293,9 @@ def _device_regulate_eig(covs, svdcut, want_prec):
 def regulate_blocks(covs, svdcut, want_prec=False, engine=None):
     """[cov] -> [_Block]: the factorisations of every correlated block, on the device when one is
     visible (``engine`` None), grouped by block size: Cholesky where the svdcut floor touches no
-    mode, the batched eigensolver for the blocks that hands back (up to EIGH_DEVICE_MAX rows, at
-    least EIGH_DEVICE_MIN_BLOCKS of one size: :func:`_eigh_on_device`).  LAPACK eigen route for the
+    mode, the batched eigensolvers for the blocks that hands back (up to EIGH_DEVICE_MAX rows at
+    least EIGH_DEVICE_MIN_BLOCKS of one size, up to EIGH_LARGE_MAX rows where measured or asked for:
+    :func:`_eigh_on_device`).  LAPACK eigen route for the
     others, for a block the eigensolver hands on (``'eig_handed_back'`` is set on it: it was solved
     twice) and for ``engine='host'`` / ``'eig'``."""
     if engine is None:
