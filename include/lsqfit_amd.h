@@ -405,6 +405,15 @@ int lsqamd_op_gemm_tn(void *stream, int64_t M, int64_t N, int64_t K, double alph
 int lsqamd_op_potrf_upper(void *stream, double *A, int64_t n, int64_t lda, int64_t n_cols,
                           double *work, size_t work_bytes, int32_t *dev_info);
 size_t lsqamd_op_potrf_work_bytes(int64_t n);
+/* the pivot solver of the block-Jacobi eigensolver on its own (eigh_twosided.hip: two-sided Jacobi in LDS, one workgroup per
+ * matrix): nb symmetric B x B matrices, 2 <= B <= 64 (LSQAMD_EINVAL outside), matrix b at A + b * strideA with leading
+ * dimension lda >= B, strideA >= (B - 1) * lda + B when nb > 1 (no overlap; LSQAMD_EINVAL otherwise); only the upper
+ * triangle is read.  A_b is overwritten with its orthonormal eigenvectors as columns in ascending eigenvalue order (ties by
+ * index), lam[nb][B] ascending, sweeps[nb], status[nb] = 0, or 1 without a rotation-free sweep within 30 sweeps or with a
+ * value that is not finite.  Indefinite and singular matrices are ordinary inputs.  Device pointers; asynchronous on the
+ * stream. */
+int lsqamd_op_eigh_pivots(void *stream, int64_t B, int32_t nb, double *A, int64_t lda, int64_t strideA, double *lam,
+                          int32_t *sweeps, int32_t *status);
 /* the batched engine's symmetric product on its packed 128 x 128 tiles (dogleg family): y[b] = A[b] u[b], quad[b] = u[b]^T A[b] u[b]
  * for the fits with active[b] != 0 (the others' outputs are left alone).  A[n_fits][P][P] dense row-major, of which only the
  * upper triangle is read; u, y [n_fits][P]; quad [n_fits]; device pointers.  Deterministic (no floating-point atomics).

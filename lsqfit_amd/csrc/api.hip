@@ -768,6 +768,14 @@ int lsqamd_op_potrf_upper(void *stream, double *A, int64_t n, int64_t lda, int64
              ? 0 : LSQAMD_EHIP;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(nullptr);)
 
+int lsqamd_op_eigh_pivots(void *stream, int64_t B, int32_t nb, double *A, int64_t lda, int64_t strideA, double *lam,
+                          int32_t *sweeps, int32_t *status) try {
+  if (B < 2 || B > 64 || nb < 1 || lda < B || !A || !lam || !sweeps || !status) return LSQAMD_EINVAL;
+  if (nb > 1 && strideA < (B - 1) * lda + B) return LSQAMD_EINVAL;     // overlapping matrices: the workgroups would race
+  return launch_eigh_twosided(reinterpret_cast<hipStream_t>(stream), A, B, lda, strideA, nb, lam, sweeps, status) == hipSuccess
+             ? 0 : LSQAMD_EHIP;
+} LSQAMD_ABI_CATCH(return lsqamd::abi_exception(nullptr);)
+
 int64_t lsqamd_nf(const lsqamd_fit *f) try {
   if (!f) return 0;
   int64_t nf = f->N;

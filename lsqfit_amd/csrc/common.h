@@ -239,8 +239,17 @@ constexpr int64_t kEighBlocksMax = 256;
 size_t eigh_blocks_slab_doubles(int64_t B, int64_t lda);
 hipError_t launch_eigh_blocks(hipStream_t st, double *A, int64_t B, int64_t lda, int64_t strideA, int32_t nb, double *slab,
                               double *lam, int32_t *sweeps, int32_t *status);
+// the same contract for 2 <= B <= 64 (eigh_twosided.hip: classical two-sided Jacobi in LDS, one workgroup per matrix; the upper
+// triangle of A_b is read).  It works on A itself, so an indefinite or singular matrix is an ordinary input: status 1 only
+// without a rotation-free sweep within 30 sweeps, or for an entry or eigenvalue that is not finite.  A row and column that are
+// exactly zero off the diagonal stay exactly decoupled, and their unit vector comes back bit for bit.
+// floor (optional): floor[b] in device memory, read when the kernel runs; a pair of matrix b is also left alone at or below
+// it.  For matrices that are pivots of a larger one (eigh_large.hip): what is noise on the scale of the matrix the pivots
+// were cut from is not rotated, however small the pivot itself is.
+hipError_t launch_eigh_twosided(hipStream_t st, double *A, int64_t B, int64_t lda, int64_t strideA, int32_t nb,
+                                double *lam, int32_t *sweeps, int32_t *status, const double *floor = nullptr);
 // the same contract for kEighBlocksMax < B <= kEighLargeMax (eigh_large.hip: two-sided block Jacobi, rotations on fp64 MFMA,
-// the 64 x 64 pivots through launch_eigh_blocks).  A_b needs room for Bp = B rounded up to 32 rows and columns: lda >= Bp,
+// the 64 x 64 pivots through launch_eigh_twosided).  A_b needs room for Bp = B rounded up to 32 rows and columns: lda >= Bp,
 // strideA >= Bp * lda (the padding is overwritten).  scratch: eigh_large_scratch_doubles(B, nb) doubles for ALL nb matrices;
 // its first nb * Bp * Bp doubles are free for the caller again when the call returns.  Synchronises the stream once per sweep.
 constexpr int64_t kEighLargeMax = 8192;

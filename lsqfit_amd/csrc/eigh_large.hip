@@ -9,7 +9,7 @@
 // matrices and all pairs:
 //
 //   gather   P = [A_II A_IJ; A_JI A_JJ]                      64 x 64 per pair, contiguous
-//   solve    launch_eigh_blocks on the batch of P            P <- Q, orthonormal eigenvectors (LDS-resident solver)
+//   solve    launch_eigh_twosided on the batch of P          P <- Q, orthonormal eigenvectors (two-sided Jacobi in LDS)
 //   polish   Q <- Q (3 I - Q^T Q) / 2                        polish_kernel (see below)
 //   columns  X[:, I u J] <- X[:, I u J] Q   for X = A and V  rotate_kernel<false>
 //   rows     A[I u J, :] <- Q^T A[I u J, :]                  rotate_kernel<true>
@@ -28,21 +28,20 @@
 //
 // Ragged B: the padding rows and columns of A hold zeros off the diagonal and -1 on it, those of V the unit matrix.
 // A rotation between columns that are both exactly zero in a row keeps that row zero, and the inner solver never
-// rotates a column that is exactly orthogonal to all others (its test is |g_p . g_q| > tol ...): the padding stays
+// rotates a pair whose off-diagonal entry is exactly zero (its test is |a_pq| > eps |P|_F / 64): the padding stays
 // EXACTLY decoupled -- Q holds the unit vectors of the padding indices bit for bit, wherever the ascending order of
 // Q's columns moves them.  At the end a column j is a padding column iff V[k][j] == 1 for a padding row k; those are
 // left out of the sort.  |A|_F excludes them (each contributes exactly 1 to the sum of squares).
 //
-// The pivot is shifted before it is solved: gather adds sigma = kShift B eps |A|_F to its diagonal (|A|_F is measured
-// once, ahead of the first sweep).  The inner solver is one-sided: it orthogonalises the columns of G = P V, which
-// diagonalises P^2, and eigenvalues +l and -l' of an indefinite P that agree in magnitude are degenerate there -- their
-// eigenvectors stay mixed (the inner solver's own no-eigenvector test reports it, status 1).  The pivots of a singular
-// covariance are of that kind as soon as its null space has gathered into whole column blocks: a null-null pivot is
-// rounding noise of either sign.  Unshifted, such pivots are not diagonalised, and the quadratic tail of the iteration
-// becomes a linear one of a factor 2 per sweep (measured, profiles/eigh_large.txt: 23 sweeps at 320 rows, more than 30 from
-// 512 on).  sigma lies far above that noise (a few eps |A|) and far below every eigenvalue that means anything, so P + sigma
-// is definite wherever P is semidefinite to rounding; its eigenvectors are P's, and what the inner solver's stopping test
-// leaves of the pivot's off-diagonal, <= 32 eps sigma where the shift matters, is nothing against the stopping level here.
+// The inner solve is launch_eigh_twosided (eigh_twosided.hip): classical two-sided Jacobi on the pivot itself, in LDS.  The
+// pivots of a singular covariance are indefinite as soon as its null space has gathered into whole column blocks (a
+// null-null pivot is rounding noise of either sign); to that solver they are ordinary input, and the pivot goes to it as
+// it is gathered, with one addition: a floor on its rotation test from the norm of the whole matrix (kPivotFloor).  Until
+// then the inner solve was the one-sided solver of eigh_blocks.hip, which diagonalises P^2 and cannot separate eigenvalues
+// +l and -l' that agree in magnitude; it needed a diagonal shift of the pivot and still handed back singular blocks from
+// 1024 rows on (profiles/eigh_large.txt).  That arithmetic stays reachable for measurements: LSQAMD_EIGH_LARGE_INNER=onesided
+// (read per call) gathers with the shift sigma = kShiftOneSided B eps |A|_F and solves with launch_eigh_blocks.
+// profiles/eigh_pivots.txt holds the two side by side.
 //
 // A matrix that has met the stopping test is frozen (the done words go to the device after the sweep): rotate_kernel leaves
 // it alone and polish_kernel no longer collects status words for it, so what the caller gets does not depend on how long the
@@ -54,9 +53,13 @@
 // its inner solves came back with status 1 (polish_kernel collects the words), or an eigenvalue is not finite.
 //
 // Between solve and columns one more launch, polish_kernel, makes Q orthonormal to rounding (one Newton-Schulz step on
-// MFMA): measured without it, the 64 eps the inner solver's Q is off by add up over the (nblk - 1) x sweeps similarities
-// to 7-14 B eps lam_max in the eigenvalues; with it every defect is at most 0.44 of max(B eps lam_max, LAPACK's own defect).
+// MFMA): measured without it (one-sided inner solver), the 64 eps the inner solver's Q is off by add up over the (nblk - 1) x
+// sweeps similarities to 7-14 B eps lam_max in the eigenvalues; with it every defect is at most 0.44 of max(B eps lam_max,
+// LAPACK's own defect), with either inner solver.  The two-sided solver's rotations accumulate in V the same way; whether its
+// defects would hold without the polish has not been measured, so the polish stays.
 #include <cmath>
+#include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "common.h"
@@ -73,20 +76,24 @@ typedef double v4d __attribute__((ext_vector_type(4)));
 
 constexpr int kMaxSweeps = 30;
 constexpr double kEps = 2.220446049250313e-16;
-// Stopping factor.  The iteration has a fixed point: the inner solver leaves a pair alone below a cosine of 64 eps, and
-// measured (profiles/eigh_large.txt) off(A)_F then sits at 0.17-0.28 B eps |A|_F for the test matrices of 257..513 rows, bit
-// for bit from sweep to sweep, with every defect at most 0.44 of the tests' unit.  A factor below that level would never be met; 1
-// is met one or two sweeps before the fixed point.
+// Stopping factor.  The iteration has a fixed point: the inner solver leaves a pair alone below its thresholds.  Measured with
+// the one-sided inner solver (profiles/eigh_large.txt) off(A)_F then sat at 0.17-0.28 B eps |A|_F for the test matrices of
+// 257..513 rows, bit for bit from sweep to sweep; a factor below that level would never be met, 1 was met one or two sweeps
+// before the fixed point.  With the two-sided inner solver the sweep that meets 1 ends at about 0.01 for singular blocks of
+// 320..2048 rows (profiles/eigh_pivots.txt 3) and every defect of the tests stays below 0.44 of their unit, so the factor stays.
 constexpr double kOffTol = 1.0;
-// Pivot shift in units of B eps |A|_F (see the header).  A numpy model of this iteration and of eigh_jacobi_kernel, singular
-// blocks of 320 and 512 rows: 1 still leaves a few indefinite pivots per sweep, 16 and 256 none, with the same sweep count.
-// On the device (profiles/eigh_large.txt) 64 leaves none up to 513 rows and in 15 of 16 blocks of 512.  At 1024 and 2048 rows
-// inner solves still return status 1 and most singular blocks are handed back, although their sweeps end below the
-// stopping level: at 1024 rows through the inner solver's no-eigenvector test (the solves themselves converge), at 2048 rows
-// through that and through unconverged inner solves.  THE CAUSE IS NOT FOUND: sigma is five orders of magnitude above the
-// rounding noise there, and the model, which reproduces the unshifted iteration, shows no status word at 1024 rows with
-// this shift.  A shift of 1024 brought status 1 back at 513 rows (cause not found either), so 64 stays.
-constexpr double kShift = 64.0;
+// The inner solver leaves a pair alone at or below kPivotFloor eps |A|_F, |A|_F of the WHOLE matrix (gather_kernel writes
+// the level per pivot), besides its own test against the pivot's norm.  Without it a null-null pivot of a singular block
+// -- rounding noise and nothing else, so its own norm is no scale -- is diagonalised by rotations of arbitrary angle, which
+// (as we read it) carry the range-null coupling that the sweep has not reached yet back into the blocks it has already
+// cleared.  What is measured (profiles/eigh_pivots.txt 3): without the floor the tail is linear, a factor 5.5 / 1.9 / 1.5
+// per sweep at 320 / 1024 / 2048 rows (13 / 26 / more than 30 sweeps); with the floor 9 / 11 / 13 sweeps.  1 / 32:
+// everything the floor ever skips sums to off(A)_F <= Bp eps |A|_F / 32, a 32nd of the stopping level; a floor of 1 was
+// measured too and saves one more sweep, with nothing left between it and kOffTol.
+constexpr double kPivotFloor = 1.0 / 32.0;
+// LSQAMD_EIGH_LARGE_INNER=onesided only: the pivot shift in units of B eps |A|_F that the one-sided inner solver needs (see
+// the header; 64 left no indefinite pivot up to 513 rows, profiles/eigh_large.txt).
+constexpr double kShiftOneSided = 64.0;
 constexpr int kBlk = 32, kPiv = 64;
 constexpr int LDQ = 80;                       // Q in LDS: rows 16 doubles apart mod 32 banks (4 k-rows x 16 columns per read)
 constexpr int LDT_COL = 68, LDT_ROW = 80;     // the tile: read by rows of 4 k (columns role) or like Q (rows role)
@@ -126,11 +133,15 @@ __global__ __launch_bounds__(256) void pad_init_kernel(Large g, int32_t *ibad, i
   }
 }
 
-// grid (npairs, nb): the pair's pivot, 64 x 64 contiguous, plus shift * |A_b|_F on its diagonal (rec: offnorm_kernel's
-// record, npad: the padding's share of it)
-__global__ __launch_bounds__(256) void gather_kernel(Large g, int s, const double *rec, double shift, double npad) {
+// grid (npairs, nb): the pair's pivot, 64 x 64 contiguous, as it is, and floor[pivot] = level * |A_b|_F for the inner
+// solver's rotation test (rec: offnorm_kernel's record, npad: the padding's share of it).  SHIFT (the one-sided inner solver
+// only): no floor, level * |A_b|_F goes on the pivot's diagonal instead
+template <bool SHIFT>
+__global__ __launch_bounds__(256) void gather_kernel(Large g, int s, const double *rec, double level, double npad,
+                                                     double *floor) {
   const int64_t b = blockIdx.y;
-  const double sigma = shift * sqrt(rec[2 * b] + rec[2 * b + 1] - npad);
+  const double sigma = level * sqrt(rec[2 * b] + rec[2 * b + 1] - npad);
+  if (!SHIFT && threadIdx.x == 0) floor[b * g.npairs + blockIdx.x] = sigma;
   int p, q;
   pair_of(g.n, s, (int)blockIdx.x + g.slot0, p, q);
   const double *a = g.A + b * g.strideA;
@@ -139,7 +150,8 @@ __global__ __launch_bounds__(256) void gather_kernel(Large g, int s, const doubl
   const int64_t col = c < kBlk ? p * kBlk + c : q * kBlk + c - kBlk;
   for (int r = threadIdx.x >> 6; r < kPiv; r += 4) {
     const int64_t row = r < kBlk ? p * kBlk + r : q * kBlk + r - kBlk;
-    out[r * kPiv + c] = a[row * g.lda + col] + (r == c ? sigma : 0.0);
+    const double v = a[row * g.lda + col];
+    out[r * kPiv + c] = SHIFT && r == c ? v + sigma : v;
   }
 }
 
@@ -347,7 +359,7 @@ __global__ __launch_bounds__(256) void scatter_kernel(Large g, const double *key
 }
 
 struct Scratch {
-  double *V, *piv, *ilam, *rowsq, *rec, *key;
+  double *V, *piv, *ilam, *rowsq, *rec, *key, *floor;
   int32_t *src, *isweeps, *istatus, *done, *ibad;
   size_t doubles;
 };
@@ -372,6 +384,7 @@ Scratch carve(int64_t B, int64_t nb, double *base) {
   s.istatus = (int32_t *)take((size_t)(nb * npairs + 1) / 2);
   s.done = (int32_t *)take((size_t)(nb + 1) / 2);
   s.ibad = (int32_t *)take((size_t)(nb + 1) / 2);
+  s.floor = take((size_t)(nb * npairs));                    // per pivot: the floor of the inner solver's rotation test
   s.doubles = off;
   return s;
 }
@@ -424,17 +437,27 @@ hipError_t launch_eigh_large(hipStream_t st, double *A, int64_t B, int64_t lda, 
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsRow);
     }));
   }
-  const double thr = kOffTol * (double)B * kEps, npad = (double)(Bp - B), shift = kShift * (double)B * kEps;
+  const double thr = kOffTol * (double)B * kEps, npad = (double)(Bp - B), shift = kShiftOneSided * (double)B * kEps;
+  const char *inner = std::getenv("LSQAMD_EIGH_LARGE_INNER");        // read per call; anything but "onesided": the default
+  const bool onesided = inner && std::strcmp(inner, "onesided") == 0;
   hipLaunchKernelGGL(pad_init_kernel, dim3((unsigned)Bp, unb), dim3(256), 0, st, g, sc.ibad, sc.done);
-  // |A|_F for the pivot shift; every sweep's record replaces it with the same number to rounding
+  // |A|_F for the inner solver's floor (the pivot shift); every sweep's record replaces it with the same number to rounding
   hipLaunchKernelGGL(rownorm_kernel, dim3((unsigned)((Bp + 3) / 4), unb), dim3(256), 0, st, g, nb, sc.rowsq);
   hipLaunchKernelGGL(offnorm_kernel, dim3(unb), dim3(256), 0, st, g, nb, sc.rowsq, sc.rec);
   ECHK(hipGetLastError());
   int32_t open = nb;
   for (int sweep = 0; sweep < kMaxSweeps && open > 0; ++sweep) {
     for (int s = 0; s < g.n - 1; ++s) {
-      hipLaunchKernelGGL(gather_kernel, dim3((unsigned)g.npairs, unb), dim3(256), 0, st, g, s, sc.rec, shift, npad);
-      ECHK(launch_eigh_blocks(st, sc.piv, kPiv, kPiv, kPiv * kPiv, nb * g.npairs, nullptr, sc.ilam, sc.isweeps, sc.istatus));
+      if (onesided) {
+        hipLaunchKernelGGL(gather_kernel<true>, dim3((unsigned)g.npairs, unb), dim3(256), 0, st, g, s, sc.rec, shift, npad,
+                           sc.floor);
+        ECHK(launch_eigh_blocks(st, sc.piv, kPiv, kPiv, kPiv * kPiv, nb * g.npairs, nullptr, sc.ilam, sc.isweeps, sc.istatus));
+      } else {
+        hipLaunchKernelGGL(gather_kernel<false>, dim3((unsigned)g.npairs, unb), dim3(256), 0, st, g, s, sc.rec,
+                           kPivotFloor * kEps, npad, sc.floor);
+        ECHK(launch_eigh_twosided(st, sc.piv, kPiv, kPiv, kPiv * kPiv, nb * g.npairs, sc.ilam, sc.isweeps, sc.istatus,
+                                  sc.floor));
+      }
       hipLaunchKernelGGL(polish_kernel, dim3((unsigned)(nb * g.npairs)), dim3(256), kLdsRow, st, sc.piv, sc.istatus, sc.done,
                          sc.ibad, g.npairs);
       hipLaunchKernelGGL(rotate_kernel<false>, dim3(tiles, (unsigned)g.npairs, 2 * unb), dim3(256), kLdsCol, st, g, s, sc.done);

@@ -216,7 +216,9 @@ EIGH_DEVICE_MIN_BLOCKS = 64
 
 # Above EIGH_DEVICE_MAX rows (profiles/eigh_large.txt): (first size, last size, fewest blocks) of the ranges in which the
 # device route was measured faster than LAPACK at every size and every batch scanned; everywhere else it stays behind
-# LSQAMD_EIGH_LARGE=device.
+# LSQAMD_EIGH_LARGE=device.  Still empty: profiles/eigh_pivots.txt (the two-sided pivot solver) has the route at
+# 0.38-0.63 x LAPACK for 16 blocks of 512 / 1024 rows, 4 of 2048 and one of 4096, and at 1.1-7.1 x for fewer or smaller;
+# ranges from that: to be done.
 EIGH_LARGE_DEFAULT = ()
 
 

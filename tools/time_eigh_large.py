@@ -25,7 +25,8 @@ shapes = sys.argv[2:] or ['512:1,4,16', '1024:1,4,16', '2048:1,4,16', '4096:1,4,
 
 
 def kernel_split(covs):
-    """one more device call under the kernel tracer: device time (ms) of the inner solves (eigh_jacobi_kernel), of the
+    """one more device call under the kernel tracer: device time (ms) of the inner solves (eigh_twosided_kernel, or
+    eigh_jacobi_kernel under LSQAMD_EIGH_LARGE_INNER=onesided), of the
     rotations (rotate_kernel, both roles) and of every other kernel of the call"""
     from torch.profiler import ProfilerActivity, profile
     with profile(activities=[ProfilerActivity.CUDA]) as prof:
@@ -34,7 +35,7 @@ def kernel_split(covs):
     t = dict(inner=0.0, rot=0.0, other=0.0)
     for e in prof.key_averages():
         us = getattr(e, 'device_time_total', None) or getattr(e, 'cuda_time_total', 0.0)
-        t['inner' if 'eigh_jacobi_kernel' in e.key else 'rot' if 'rotate_kernel' in e.key else 'other'] += us
+        t['inner' if 'eigh_jacobi_kernel' in e.key or 'eigh_twosided_kernel' in e.key else 'rot' if 'rotate_kernel' in e.key else 'other'] += us
     return tuple('%.2f ms' % (1e-3 * t[k]) for k in ('inner', 'rot', 'other'))
 
 
