@@ -425,6 +425,16 @@ int lsqamdb_op_symv_packed(void *stream, int64_t P, int32_t n_fits, const double
  * pivoted recipe (_gsl.pyx:704-706), 1: the thresholded pseudo-inverse of _scipy.py:170-175.  Host pointers, no GPU. */
 int lsqamd_op_truncated_inverse(const double *G, int64_t n, int64_t n_rows, int32_t scipy_form, double *cov_out,
                                 int32_t *dropped);
+/* the same pivoted recipe (gsl_multifit_nlinear_covar(J, 0.0), _gsl.pyx:704-706) on the device (rankdef_dev.hip: blocked
+ * Cholesky with diagonal pivoting and a rank exit, then the positive-definite chain on the kept block): G[n][ld] symmetric
+ * with both triangles valid, overwritten by the factor as far as it got; cov[n][ldc] = inv(G[S, S]) embedded in zeros,
+ * S = perm[:rank] in pivot order (ties: the lowest index); perm[n]; rank[0] = the rank, rank[1] = 0, 1 for a diagonal entry
+ * that is not finite, 2 when the kept block had no Cholesky factor (cov is then not to be used).  1 <= n <= 8192
+ * (LSQAMD_EUNSUPPORTED above); work: lsqamd_op_pivoted_inverse_dev_work_bytes(n) bytes (0 for an n outside the range),
+ * 16-byte aligned.  Device pointers; asynchronous on the stream. */
+int lsqamd_op_pivoted_inverse_dev(void *stream, double *G, int64_t n, int64_t ld, double *cov, int64_t ldc, int32_t *perm,
+                                  int32_t *rank, double *work, size_t work_bytes);
+size_t lsqamd_op_pivoted_inverse_dev_work_bytes(int64_t n);
 
 /* ---- results (replace vector2array / matrix2array, _gsl.pyx:77-86,:104-120) ---- */
 int lsqamd_get_x(lsqamd_fit *fit, double *out, size_t cap);       /* P        : fit.x  */

@@ -103,6 +103,8 @@ PROTOTYPES = {
     'lsqamd_op_eigh_pivots': (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp]),
     'lsqamdb_op_symv_packed': (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     'lsqamd_op_truncated_inverse': (C.c_int, [_dp, C.c_int64, C.c_int64, C.c_int32, _dp, C.POINTER(C.c_int32)]),
+    'lsqamd_op_pivoted_inverse_dev': (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, C.c_size_t]),
+    'lsqamd_op_pivoted_inverse_dev_work_bytes': (C.c_size_t, [C.c_int64]),
     'lsqamd_get_x': (C.c_int, [_vp, _dp, C.c_size_t]),
     'lsqamd_get_f': (C.c_int, [_vp, _dp, C.c_size_t]),
     'lsqamd_get_J': (C.c_int, [_vp, _dp, C.c_size_t]),

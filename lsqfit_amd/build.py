@@ -16,7 +16,7 @@ OBJ = os.path.join(HERE, 'build')
 LIB = os.path.join(HERE, 'liblsqfit_amd.so')
 SOURCES = ['gemm_tn_f64.hip', 'chol.hip', 'potf2_mfma.hip', 'model.hip', 'vecops.hip', 'api.hip', 'pool.hip', 'workspace.hip',
            'eval.hip', 'lm_driver.hip', 'scipy_methods.hip', 'batch.hip', 'batch_trs.hip', 'comm.hip', 'whiten.hip', 'qr.hip', 'jit.hip',
-           'rankdef.hip', 'robust.hip', 'eigh_blocks.hip', 'eigh_large.hip', 'eigh_twosided.hip']
+           'rankdef.hip', 'rankdef_dev.hip', 'robust.hip', 'eigh_blocks.hip', 'eigh_large.hip', 'eigh_twosided.hip']
 # per-file code-generation switches (reasons in the files' headers)
 EXTRA = {'potf2_mfma.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form']}
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']

@@ -279,6 +279,8 @@ int do_reduce(lsqamd_fit *f, double *buf, int64_t count);
 int do_covariance(lsqamd_fit *f);
 int do_covariance_qr(lsqamd_fit *f);
 int covariance_rank_deficient(lsqamd_fit *f);   // rankdef.hip
+int covariance_rank_deficient_dev(lsqamd_fit *f);   // rankdef_dev.hip: the GSL form on the device
+bool rankdef_dev_supports(int64_t P);
 // (A + mu D^2) v = g through the CholeskyQR factor of [J ; W_prior ; sqrt(mu) D] (qr.hip): v -> f->yv[P..2P)
 int solve_damped_qr(lsqamd_fit *f, double mu);
 size_t qr_work_bytes(const lsqamd_fit *f);

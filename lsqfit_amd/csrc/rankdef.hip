@@ -12,8 +12,10 @@
 // Both work from G = J^T J (+ prior precision), whose entries carry rounding noise of P eps max|G|:
 // a direction counts as null when its pivot / eigenvalue is below that floor (the reference's own
 // thresholds -- 0 and (eps max(shape))^2 in these units -- lie below it; for a column that is exactly
-// zero, the reference's test case, the results are identical).  This is the rare path: it runs on the
-// host (O(P^3) on one core), only after the device factorisation has met a non-positive pivot.
+// zero, the reference's test case, the results are identical).  This path runs only after the device
+// factorisation has met a non-positive pivot.  The arithmetic in this file is the host's (O(P^3) on one core):
+// the scipy form always, the GSL form up to LSQAMD_RANKDEF_MAXP parameters; above that, or with
+// LSQAMD_RANKDEF=device, the GSL form runs on the device (rankdef_dev.hip).
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -145,10 +147,18 @@ int covariance_rank_deficient(lsqamd_fit *f) {
   const int64_t P = f->P;
   const bool scipy = f->opt.trs >= LSQAMD_TRS_TRF;
   static const int64_t cap = [] { const char *e = getenv("LSQAMD_RANKDEF_MAXP"); return e ? atoll(e) : (int64_t)2048; }();
-  if (P > (scipy ? std::min<int64_t>(cap, 1024) : cap)) return LSQAMD_EUNSUPPORTED;   // O(P^3) on one host core
   if (f->comm || f->reduce) {
-    // every rank holds the same reduced G and runs the same host arithmetic: identical results, no exchange
+    // every rank holds the same reduced G and runs the same arithmetic -- the host's, or the device route's deterministic
+    // kernels (no atomics, one fixed summation order): identical results, no exchange
   }
+  if (!scipy) {
+    // LSQAMD_RANKDEF (read per call): device = rankdef_dev.hip at any P, host = this file's arithmetic and its refusal above
+    // the cap; unset: the device route exactly where the host route refuses
+    const char *route = getenv("LSQAMD_RANKDEF");
+    const bool force_dev = route && !strcmp(route, "device"), force_host = route && !strcmp(route, "host");
+    if ((force_dev || (!force_host && P > cap)) && rankdef_dev_supports(P)) return covariance_rank_deficient_dev(f);
+  }
+  if (P > (scipy ? std::min<int64_t>(cap, 1024) : cap)) return LSQAMD_EUNSUPPORTED;   // O(P^3) on one host core
   // G = J^T J (+ prior), dense, from the packed tiles the fit holds
   HIPCHK(f, launch_unpack_sym(f->st, f->redbuf, P, f->Wl, f->ldm));
   f->have_dense_A = false;
