@@ -521,6 +521,13 @@ int lsqamdb_set_options(lsqamdb_fits *fits, const lsqamd_options *opt);
 /* p0[B*P]; summaries[B] or NULL (t_setup_ms carries the number of graph-replayed rounds) */
 int lsqamdb_run(lsqamdb_fits *fits, const double *p0, lsqamd_summary *summaries, int32_t use_graph);
 int lsqamdb_get_x(lsqamdb_fits *fits, double *out, size_t cap);                         /* B*P */
+/* covariance and log det(J^T J + prior precision) of every fit at its final point.  options.solver = LSQAMD_SOLVER_CHOLESKY:
+ * from the normal equations.  LSQAMD_SOLVER_QR (n_param <= 32; lsqamdb_set_options refuses more with LSQAMD_EUNSUPPORTED):
+ * from a Householder factorisation of the whitened Jacobian stacked on the prior's rows (csrc/batch_qr.hip), error
+ * ~ cond(J) eps instead of cond(J)^2 eps; the fits' steps stay on the damped normal equations, so x, chi2 and nit do not
+ * depend on the solver.  A fit whose factorisation fails (rank-deficient Jacobian without a prior) gets NaN in both;
+ * the other fits of the batch are not affected.  After lsqamdb_set_options has changed the solver, lsqamdb_run comes first
+ * (LSQAMD_EINVAL otherwise).  With the timers on, which = LSQAMD_T_COVAR of lsqamdb_timing_get brackets this call's launches. */
 int lsqamdb_covariance(lsqamdb_fits *fits, double *logdet_jtj_out, size_t cap);         /* B */
 int lsqamdb_get_cov(lsqamdb_fits *fits, int32_t fit, double *out, size_t cap);          /* P*P */
 int lsqamdb_get_cov_all(lsqamdb_fits *fits, double *out, size_t cap);                    /* n_fits*P*P, one copy */

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _lib
 from .fit import gammaQ
-from .fitter import _ALGS, _SCALERS, normalize_tol
+from .fitter import _ALGS, _SCALERS, _SOLVERS, normalize_tol
 from .models import MODEL_IDENTITY, MODEL_TAPE
 
 
@@ -160,9 +160,10 @@ class BatchedFits:
         self._check(self.lib.lsqamdb_timing_enable(self.h, int(bool(on))), 'timing_enable')
 
     def timings(self):
-        """-> {'syrk': (total ms, launches), 'cholesky': (...)} since ``timing(True)``"""
+        """-> {'syrk': (total ms, launches), 'cholesky': (...), 'covar': (...: the launches of the covariance call)} since
+        ``timing(True)``"""
         out = {}
-        for name, which in (('syrk', 3), ('cholesky', 6)):
+        for name, which in (('syrk', 3), ('cholesky', 6), ('covar', 8)):
             ms, n = C.c_double(0.0), C.c_int64(0)
             self._check(self.lib.lsqamdb_timing_get(self.h, which, C.byref(ms), C.byref(n)), 'timing_get')
             out[name] = (ms.value, n.value)
@@ -232,11 +233,17 @@ class BatchedFits:
         self._check(self.lib.lsqamdb_set_priors(self.h, _lib.dptr(mean), _lib.anyptr(prec)), 'set_priors')
 
     def run(self, p0=None, tol=1e-8, maxit=1000, scaler='more', factor_up=3.0, factor_down=2.0,
-            use_graph=True, covariance=True, alg='lm'):
+            use_graph=True, covariance=True, alg='lm', solver='cholesky'):
         """-> dict of arrays: pmean[B,P], chi2, dof, Q, logGBF, nit, stopping_criterion, status,
         nfev (+ psdev[B,P] and cov(b) when ``covariance``).  ``alg``: 'lm', 'dogleg', 'ddogleg' or 'subspace2D'
         (``nonlinear_fit``'s names, _gsl.pyx:622-635); 'lmaccel' is refused by the library (it needs one more residual
-        evaluation per trial).  Small batches that plain LM runs as one launch take the lockstep rounds with the others."""
+        evaluation per trial).  Small batches that plain LM runs as one launch take the lockstep rounds with the others.
+        ``solver``: 'cholesky', or 'qr' (the reference's default, _gsl.pyx:571,646-647; fits of up to 32 parameters): ``cov``,
+        ``psdev`` and ``logGBF`` then come from a Householder factorisation of the whitened Jacobian (csrc/batch_qr.hip), error
+        ~ cond(J) eps instead of cond(J)^2 eps; the steps stay on the damped normal equations, so ``pmean``, ``chi2`` and ``nit``
+        are those of 'cholesky'.  A fit whose Jacobian is rank deficient has NaN there; the others are unaffected."""
+        if solver not in ('cholesky', 'qr'):
+            raise ValueError("unknown solver %r: the batched engine has 'cholesky' and 'qr'" % (solver,))
         if alg not in _ALGS:
             raise ValueError('unknown alg %r: the batched engine runs lm, dogleg, ddogleg and subspace2D' % (alg,))
         B, P = self.B, self.P
@@ -248,7 +255,7 @@ class BatchedFits:
             p0 = np.where(self.prior_mean != 0.0, self.prior_mean, self.prior_mean + 0.1 * self.prior_sdev)
         p0 = np.ascontiguousarray(np.broadcast_to(np.asarray(p0, np.float64), (B, P)))
         xtol, gtol, ftol = normalize_tol(tol)
-        opt = _lib.Options(xtol=xtol, gtol=gtol, ftol=ftol, maxit=int(maxit), scaler=_SCALERS[scaler], solver=0,
+        opt = _lib.Options(xtol=xtol, gtol=gtol, ftol=ftol, maxit=int(maxit), scaler=_SCALERS[scaler], solver=_SOLVERS[solver],
                            trs=_ALGS[alg], factor_up=factor_up, factor_down=factor_down, avmax=0.75)
         self._check(self.lib.lsqamdb_set_options(self.h, C.byref(opt)), 'set_options')
         summ = (_lib.Summary * B)()

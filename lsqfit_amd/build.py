@@ -16,9 +16,12 @@ OBJ = os.path.join(HERE, 'build')
 LIB = os.path.join(HERE, 'liblsqfit_amd.so')
 SOURCES = ['gemm_tn_f64.hip', 'chol.hip', 'potf2_mfma.hip', 'model.hip', 'vecops.hip', 'api.hip', 'pool.hip', 'workspace.hip',
            'eval.hip', 'lm_driver.hip', 'scipy_methods.hip', 'batch.hip', 'batch_trs.hip', 'comm.hip', 'whiten.hip', 'qr.hip', 'jit.hip',
-           'rankdef.hip', 'rankdef_dev.hip', 'robust.hip', 'eigh_blocks.hip', 'eigh_large.hip', 'eigh_twosided.hip']
+           'rankdef.hip', 'rankdef_dev.hip', 'robust.hip', 'eigh_blocks.hip', 'eigh_large.hip', 'eigh_twosided.hip', 'batch_qr.hip']
+# rows of a fit's Jacobian one workgroup of the batched QR covariance reduces (csrc/batch_qr.hip kQrChunkRows takes its value
+# from here): fits of more rows go through a second level of the reduction tree
+QR_CHUNK_ROWS = 1024
 # per-file code-generation switches (reasons in the files' headers)
-EXTRA = {'potf2_mfma.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form']}
+EXTRA = {'potf2_mfma.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'], 'batch_qr.hip': ['-DLSQAMDB_QR_CHUNK_ROWS=%d' % QR_CHUNK_ROWS]}
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 
 
@@ -50,7 +53,8 @@ def build(force=False, verbose=False):
         s = os.path.join(CSRC, src)
         o = os.path.join(OBJ, src.replace('.hip', '.o'))
         objs.append(o)
-        if force or not _newer(o, [s] + headers):
+        # (a file with switches of its own also depends on this recipe, where they are set)
+        if force or not _newer(o, [s] + headers + ([os.path.abspath(__file__)] if src in EXTRA else [])):
             jobs.append([hipcc] + FLAGS + EXTRA.get(src, []) + ['-c', s, '-o', o])
 
     def run(cmd):

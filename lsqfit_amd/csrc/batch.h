@@ -92,4 +92,15 @@ hipError_t launch_trs_step(hipStream_t st, int64_t P, int32_t B, int trs, const 
                            const int32_t *active);
 hipError_t launch_trs_decide(hipStream_t st, int32_t B, double factor_up, double factor_down, BState s, BTrs t);
 
+// ---- solver = qr: Householder TSQR covariance of small fits (batch_qr.hip) ---------------------------------------------
+constexpr int64_t kBatchQrMaxP = 32;
+int64_t batch_qr_chunks(int64_t N);   // row chunks of a fit; a function of N alone
+// cov_b = (J_b^T J_b + Lambda_b)^-1, logdet[b] = log det(J_b^T J_b + Lambda_b) from the whitened J[B][N][ld] (columns 0 .. P-1;
+// ld even and >= 8 / 16 / 32 for P <= 8 / 16 / 32).  prior: 0 none, 1 prec[B][P] diagonal, 2 prec[P][P] dense and shared.
+// scratch: B * batch_qr_chunks(N) * P * P doubles.  info[b] = 0, or j + 1: column j adds nothing to the rank (or pivot j of
+// the dense prior is not positive) -- cov_b and logdet[b] are then NaN.  Two launches, no synchronisation.
+hipError_t launch_batch_qr(hipStream_t st, const double *J, int64_t j_stride, int64_t ld, int64_t N, int64_t P, int32_t B,
+                           const double *prec, int prior, double *scratch, double *cov, int64_t cov_stride, int64_t ldc,
+                           double *logdet, int32_t *info);
+
 }  // namespace lsqamd

@@ -496,6 +496,7 @@ struct lsqamdb_fits {
   double *yv = nullptr, *partial = nullptr, *spart = nullptr, *Wl = nullptr, *cov = nullptr, *logdet = nullptr;
   int32_t *syrk_map = nullptr;
   int32_t syrk_nwork = 0;
+  double *qr_scratch = nullptr;   // solver = qr: the chunk R's of batch_qr.hip where chol_work is too small for them
   BState s;
   BTrs t;                    // the dogleg family's per-fit state (batch_trs.hip)
   bool have_x = false, have_data = false, have_prior = false, have_tape = false, ran = false, have_cov = false;
@@ -506,10 +507,11 @@ struct lsqamdb_fits {
   // phase timers (lsqamdb_timing_enable): HIP events around the J^T J launch and the batched factorisation of every round;
   // rounds then run eagerly (events are not recorded into a captured graph)
   bool timing = false;
-  EventPairs tm_syrk, tm_chol;
+  EventPairs tm_syrk, tm_chol, tm_cov;   // (tm_cov: the launches of lsqamdb_covariance, either route)
   ~lsqamdb_fits() {
     give_events(tm_syrk, dev);
     give_events(tm_chol, dev);
+    give_events(tm_cov, dev);
   }
 };
 
@@ -532,6 +534,8 @@ hipError_t copy2d_sync(lsqamdb_fits *f, void *dst, size_t dpitch, const void *sr
   if (e != hipSuccess) return e;
   return hipStreamSynchronize(f->st);
 }
+
+int64_t qr_scratch_per_fit(int64_t N, int64_t P) { return P <= kBatchQrMaxP ? batch_qr_chunks(N) * P * P : 0; }
 
 size_t carve_b(lsqamdb_fits *f, void *ws, bool dry) {
   const lsqamd_config &c = f->cfg;
@@ -607,6 +611,9 @@ size_t carve_b(lsqamdb_fits *f, void *ws, bool dry) {
   f->t.dx_sd = cv.take<double>(B * P); f->t.dx_gn = cv.take<double>(B * P);
   f->t.part = cv.take<double>(B * symv_packed_partials(P));
   f->t.gn_failed = cv.take<int32_t>(B); f->t.lmask = cv.take<int32_t>(B);
+  // solver = qr (batch_qr.hip): the chunk R's of a fit go to its share of chol_work, which the covariance chain owns at that
+  // moment; fits of so many rows that they do not fit there get a buffer of their own
+  f->qr_scratch = cv.take<double>(qr_scratch_per_fit(N, P) > f->w_stride ? B * qr_scratch_per_fit(N, P) : 1);
   return cv.off;
 }
 
@@ -1203,6 +1210,13 @@ int lsqamdb_set_options(lsqamdb_fits *f, const lsqamd_options *opt) try {
     FAIL(f, LSQAMD_EINVAL, "set_options: bad value");
   if (opt->trs != LSQAMD_TRS_LM && opt->trs != LSQAMD_TRS_DOGLEG && opt->trs != LSQAMD_TRS_DDOGLEG && opt->trs != LSQAMD_TRS_SUBSPACE2D)
     FAIL(f, LSQAMD_EUNSUPPORTED, "set_options: the batched engine runs alg='lm', 'dogleg', 'ddogleg' and 'subspace2D' only");
+  if (opt->solver != LSQAMD_SOLVER_CHOLESKY && opt->solver != LSQAMD_SOLVER_QR) FAIL(f, LSQAMD_EINVAL, "set_options: unknown solver");
+  if (opt->solver == LSQAMD_SOLVER_QR && f->P > kBatchQrMaxP)
+    FAIL(f, LSQAMD_EUNSUPPORTED, "set_options: the batched engine's solver = qr takes fits of up to %d parameters (this batch has %lld)",
+         (int)kBatchQrMaxP, (long long)f->P);
+  // another solver: the covariances a run left are the other route's, and what the Cholesky chain would start from is only
+  // known to be there after a run made for it -- lsqamdb_covariance asks for a new run
+  if (opt->solver != f->opt.solver) f->have_cov = f->ran = false;
   f->opt = *opt;
   return 0;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
@@ -1247,7 +1261,8 @@ int lsqamdb_run(lsqamdb_fits *f, const double *p0, lsqamd_summary *summaries, in
   float ms = 0.f;
   (void)hipEventElapsedTime(&ms, span.e0, span.e1);
   f->ran = true;
-  f->have_cov = f->one_launch && f->have_cov_from_run;     // (the one-launch kernel leaves covariances and log dets behind)
+  // the one-launch kernel leaves covariances and log dets of the normal equations behind: not what solver = qr delivers
+  f->have_cov = f->one_launch && f->have_cov_from_run && f->opt.solver != LSQAMD_SOLVER_QR;
   return summaries ? write_summaries(f, summaries, ms) : 0;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
 
@@ -1258,14 +1273,35 @@ int lsqamdb_get_x(lsqamdb_fits *f, double *out, size_t cap) try {
   return 0;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
 
-/* (J^T J)^-1 of every fit at its final point + log det(J^T J); results stay on the device */
+/* (J^T J)^-1 of every fit at its final point + log det(J^T J); results stay on the device.
+ * solver = cholesky: potrf -> trtri -> product on the normal equations the run left (or what the one-launch fit kernel formed
+ * itself).  solver = qr (P <= 32): the whitened Jacobian of every fit is evaluated again at its final point and factored by
+ * Householder reflections, the prior appended as rows (batch_qr.hip: two launches for the batch) -- error ~ cond(J) eps instead
+ * of cond(J)^2 eps, after a one-launch run as after lockstep rounds; the fits' steps, and so pmean, chi2 and nit, are those of
+ * solver = cholesky.  Either way a fit whose factorisation fails (s.cholinfo[b] = pivot + 1) has NaN covariance and log det. */
 int lsqamdb_covariance(lsqamdb_fits *f, double *logdet_out, size_t cap) try {
   if (!f) return LSQAMD_EINVAL;
   if (!f->ran) FAIL(f, LSQAMD_EINVAL, "covariance: run first");
   const int64_t P = f->P;
   const int32_t B = f->B;
-  if (!(f->have_cov && f->one_launch)) {     // (else: formed by the fit kernel itself)
+  if (f->opt.solver == LSQAMD_SOLVER_QR) {
+    if (!f->have_cov) {
+      {
+        Bracket tb(f, f->tm_cov);
+        const int rc = jacobian_all(f, nullptr);
+        if (rc) return rc;
+        double *scratch = qr_scratch_per_fit(f->N, P) > f->w_stride ? f->qr_scratch : f->chol_work;
+        HIPCHK(f, launch_batch_qr(f->st, f->J, f->N * f->ld, f->ld, f->N, P, B, f->cfg.has_prior ? f->pprec : nullptr,
+                                  f->cfg.has_prior ? (f->cfg.prior_dense ? 2 : 1) : 0, scratch, f->cov, f->m_stride, f->ldm,
+                                  f->logdet, f->s.cholinfo));
+      }
+      HIPCHK(f, hipStreamSynchronize(f->st));
+      f->have_cov = true;
+    }
+  } else if (!(f->have_cov && f->one_launch)) {     // (else: formed by the fit kernel itself)
     // the first half of factor_and_solve's chain on its own: P columns instead of ncols_aug, no right-hand side, no mask
+    {
+    Bracket tb(f, f->tm_cov);
     hipLaunchKernelGGL(b_build_damped_kernel, dim3((unsigned)f->ntile, 16, (unsigned)B), dim3(256), 0, f->st, f->red,
                        f->red_stride, P, f->T, f->ldm, f->s.mu, f->diag, (const double *)nullptr, f->red_stride, f->M,
                        f->m_stride, (const int32_t *)nullptr, 0);
@@ -1282,6 +1318,7 @@ int lsqamdb_covariance(lsqamdb_fits *f, double *logdet_out, size_t cap) try {
     HIPCHK(f, launch_gemm_tn(f->st, g));
     hipLaunchKernelGGL(b_symmetrize_kernel, dim3((unsigned)((P + 255) / 256), (unsigned)P, (unsigned)B), dim3(256), 0,
                        f->st, f->cov, f->m_stride, P, f->ldm);
+    }
     HIPCHK(f, hipStreamSynchronize(f->st));
     f->have_cov = true;
   }
@@ -1347,15 +1384,16 @@ int lsqamdb_timing_enable(lsqamdb_fits *f, int32_t on) try {
   f->timing = on != 0;
   give_events(f->tm_syrk, f->dev);
   give_events(f->tm_chol, f->dev);
+  give_events(f->tm_cov, f->dev);
   return 0;
 } LSQAMD_ABI_CATCH(return lsqamd::abi_exception(f);)
 
 int lsqamdb_timing_get(lsqamdb_fits *f, int32_t which, double *total_ms, int64_t *count) try {
-  if (!f || (which != LSQAMD_T_SYRK && which != LSQAMD_T_CHOLESKY)) return LSQAMD_EINVAL;
+  if (!f || (which != LSQAMD_T_SYRK && which != LSQAMD_T_CHOLESKY && which != LSQAMD_T_COVAR)) return LSQAMD_EINVAL;
   (void)hipStreamSynchronize(f->st);
   double tot = 0.0;
   int64_t n = 0;
-  for (auto &pr : which == LSQAMD_T_SYRK ? f->tm_syrk : f->tm_chol) {
+  for (auto &pr : which == LSQAMD_T_SYRK ? f->tm_syrk : which == LSQAMD_T_CHOLESKY ? f->tm_chol : f->tm_cov) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) { tot += ms; ++n; }
   }

@@ -8,6 +8,7 @@ python -m lsqfit_amd.build > /dev/null
 OUT=$ROOT/lsqfit_amd/build/var_$NAME
 mkdir -p $OUT
 EXTRA=""; [ $SRC = potf2_mfma.hip ] && EXTRA="-mllvm -amdgpu-mfma-vgpr-form"
+[ $SRC = batch_qr.hip ] && EXTRA="-DLSQAMDB_QR_CHUNK_ROWS=$(cd $ROOT && python -c 'from lsqfit_amd.build import QR_CHUNK_ROWS; print(QR_CHUNK_ROWS)')"
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $EXTRA "$@" -c $ROOT/lsqfit_amd/csrc/$SRC -o $OUT/${SRC%.hip}.o
 OBJS=""
 for o in $ROOT/lsqfit_amd/build/*.o; do
